@@ -9,7 +9,10 @@ reference's gate (batch*max_episode_len rows) before warm-up, so every timed
 step trains.  `value` = env transitions of all ranks / wall time (max over
 ranks) with everything resident in HBM.
 
-    python bench.py                        # N=1, E=1024 (BASELINE configs[1])
+    python bench.py                        # N=1, E=1024 (BASELINE configs[1]): the headline line only
+    python bench.py --full                 # + rollout-only, kernel pass / roofline, throughput mode,
+                                           #   configs[2] share, gather stage, CPU baselines, dp_check
+    python bench.py --dump-outputs DIR     # + the last timed step's results as DIR/<name>.npy
     torchrun --nproc-per-node N bench.py --gpus N
     python bench.py --gpus N               # launches the N ranks itself (torchrun as a child)
 """
@@ -335,6 +338,47 @@ def exchange_limit_us(mode="strict", efficiency=0.8):
     return round(r1 * (1.0 / efficiency - 1.0) / m["exchanges_per_round"][mode], 2)
 
 
+DUMP_BUDGET_BYTES = 63 * 1000 * 1000   # array bytes; with the .npy headers the files stay under 64 MB
+
+
+def dump_outputs(path, r, rollout_only=False):
+    """What the timed path left after its last step, as `path`/<name>.npy: every
+    agent's parameter sets (weights, targets, Adam moments, flattened in
+    Engine.SETS order), its last update's stats (float64), the env copies'
+    positions and velocities, and the replay rows the last vector step appended
+    (this rank's).  Same arguments, same seed: the same inputs, so two builds
+    can be compared array for array.  At most DUMP_BUDGET_BYTES in all: past
+    that, the large arrays are written as a fixed, seeded sample of their
+    elements."""
+    eng = r.eng
+    arrays = {}
+    for i in range(r.n):
+        for w in eng.SETS:
+            arrays[f"agent{i}_{w}"] = np.concatenate([v.ravel() for v in eng.get_params(i, w).values()])
+        if not rollout_only:
+            arrays[f"agent{i}_update_stats"] = np.asarray(eng.stats(i), np.float64)
+    st = eng.env_state()
+    arrays["env_pos"], arrays["env_vel"] = st["pos"], st["vel"]
+    # every rollout appends num_envs rows at the ring head, from an empty ring
+    E, cap = r.num_envs, eng.capacity
+    at = (r.train_step - E + torch.arange(E, device=eng.device, dtype=torch.int64)) % cap
+    ring = eng.region("replay")[:cap * eng.row_stride].view(cap, eng.row_stride)
+    arrays["replay_rows_last_step"] = ring[at].cpu().numpy()
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_BUDGET_BYTES:
+        big = {k for k, a in arrays.items() if a.nbytes > (1 << 20)}
+        keep = (DUMP_BUDGET_BYTES - sum(a.nbytes for k, a in arrays.items() if k not in big)) \
+            / sum(arrays[k].nbytes for k in big)
+        rng = np.random.default_rng(0)
+        for k in sorted(big):
+            flat = arrays[k].ravel()
+            arrays[k] = flat[np.sort(rng.choice(flat.size, int(flat.size * keep), replace=False))]
+    os.makedirs(path, exist_ok=True)
+    for k, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), (k, a.dtype)
+        np.save(os.path.join(path, k + ".npy"), a)
+
+
 def rank_launch_plan(gpus, environ, argv, port=None):
     """How `bench.py --gpus N` becomes N ranks (maddpg_amd.launch: WORLD_SIZE set
     must equal N; unset with N > 1: a torchrun child of N fresh rank processes;
@@ -383,6 +427,14 @@ def main():
                          "1: one graph per step)")
     ap.add_argument("--no-gather-stage", action="store_true",
                     help="skip the gather-only stage figure (SURVEY 8d, rank 0 at N=1)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure and check everything else: the rollout-only "
+                         "figure, the kernel pass and roofline, throughput mode, the configs[2] share, the "
+                         "gather stage, the CPU baselines, the replicas' dp_check (each has its own --no-* "
+                         "switch); without it the run ends with the headline line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last of them computed (parameters, update "
+                         "stats, env state, appended replay rows) as DIR/<name>.npy (rank 0)")
     ap.add_argument("--launch-check", action="store_true",
                     help="print this rank's (rank, world, local rank) as JSON and exit before any GPU call "
                          "(tests the --gpus N launch on a CPU host)")
@@ -420,7 +472,6 @@ def main():
     if args.update_mode != "strict":
         eng.set_update_mode(args.update_mode)
     r.prefill()
-    kinds = [k for k in _lib.KERNEL]
 
     def one_step():
         if args.rollout_only:
@@ -458,11 +509,55 @@ def main():
         t = torch.tensor([dt], dtype=torch.float64, device="cuda")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
+    r.synchronize()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, r, args.rollout_only)
+    env_steps = args.num_envs * args.steps * world
+    updates = rounds * r.n           # optimiser updates (each on world*B samples)
+    value = env_steps / dt
+    lib_hash = lib_sha256()
+    head = {
+        "lib_sha256": lib_hash,
+        "metric": (f"env-steps/sec (end-to-end at the reference update cadence), {args.scenario} N={r.n}, "
+                   f"batch {args.batch_size}"),
+        "value": round(value, 3),
+        "unit": "env-steps/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(dt / args.steps * 1e3, 4),
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "fp32",
+        "data": "synthetic (random-init weights, device MPE env rollouts)",
+        "config": {"workload": f"{args.scenario} N={r.n}, {args.num_envs} env copies per GPU, batch "
+                               f"{args.batch_size}, {args.num_units}-unit MLPs, 1 update round per "
+                               f"{args.train_every} transitions per rank"
+                               + (f", policies {['ddpg' if q else 'maddpg' for q in eng.local_q]}"
+                                  if any(eng.local_q) else ""),
+                   "scenario": args.scenario, "num_envs_per_gpu": args.num_envs,
+                   "global_batch": args.batch_size * world, "parallelism": f"dp{world}",
+                   "mode": "rollout-only" if args.rollout_only else args.update_mode,
+                   "step_graph_group": args.step_group if groups else 1},
+        "trainer_updates_per_sec": round(updates / dt, 3),
+        "rounds_per_sec": round(rounds / dt, 3),
+        "update_rounds": rounds,
+        "dp": r.dp_kind if world > 1 else None,
+    }
+    if not args.full:
+        # the plain run: nothing beyond what the headline figure needs
+        if rank == 0:
+            print(json.dumps(head))
+        if world > 1:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
+    kinds = [k for k in _lib.KERNEL]
     # the run validates itself: every rank's ms/step, the communicator the
     # exchange ran over, and bit-identical replicas (strict data parallelism
     # keeps every rank's weights, targets, Adam moments and beta powers equal).
     # At N=1 the same fields describe the single replica (no communicator).
-    r.synchronize()
     info = {"ms_per_step": round(dt_local / args.steps * 1e3, 4), "checksum": eng.param_checksum(),
             "rounds": rounds}
     if world > 1:
@@ -602,9 +697,6 @@ def main():
                               "parameters, one optimizer launch (and one all-reduce) per round -- not the "
                               "reference's update order"}
 
-    env_steps = args.num_envs * args.steps * world
-    updates = rounds * r.n           # optimiser updates (each on world*B samples)
-    value = env_steps / dt
     ev_ms = event_overhead_ms(eng.stream)
     roof = None
     if launches:
@@ -615,7 +707,6 @@ def main():
                           "(hipExtLaunchKernel) in an eager pass of the same workload; the pair's two "
                           "launch durations summed")
         roof["launches_timed"] = launches
-    lib_hash = lib_sha256()
     cfg_key = f"{args.scenario}_E{args.num_envs}_B{args.batch_size}_H{args.num_units}"
     if args.num_agents is not None:
         cfg_key += f"_N{args.num_agents}"
@@ -672,34 +763,8 @@ def main():
             roof["pmc_source"] = "profiles/pmc_traffic.json"
     if rank == 0:
         out = {
-            "lib_sha256": lib_hash,
-            "metric": (f"env-steps/sec (end-to-end at the reference update cadence), {args.scenario} N={r.n}, "
-                       f"batch {args.batch_size}"),
-            "value": round(value, 3),
-            "unit": "env-steps/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": round(dt / args.steps * 1e3, 4),
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "fp32",
-            "data": "synthetic (random-init weights, device MPE env rollouts)",
-            "config": {"workload": f"{args.scenario} N={r.n}, {args.num_envs} env copies per GPU, batch "
-                                   f"{args.batch_size}, {args.num_units}-unit MLPs, 1 update round per "
-                                   f"{args.train_every} transitions per rank"
-                                   + (f", policies {['ddpg' if q else 'maddpg' for q in eng.local_q]}"
-                                      if any(eng.local_q) else ""),
-                       "scenario": args.scenario, "num_envs_per_gpu": args.num_envs,
-                       "global_batch": args.batch_size * world, "parallelism": f"dp{world}",
-                       "mode": "rollout-only" if args.rollout_only else args.update_mode,
-                       "step_graph_group": args.step_group if groups else 1},
-            "trainer_updates_per_sec": round(updates / dt, 3),
-            "rounds_per_sec": round(rounds / dt, 3),
+            **head,
             "rollout_only_env_steps_per_sec": round(rollout_only, 3),
-            "update_rounds": rounds,
-            "dp": r.dp_kind if world > 1 else None,
             "dp_check": dp_check,
             "kernel_pass": {"steps": prof_steps, "marker_pair_overhead_ms": round(ev_ms, 5),
                             "timing": "dispatch-packet events per launch; marker pairs (their overhead "

@@ -202,6 +202,10 @@ def _env_init_worker(rank, world, port, shared, q):
                       MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
     if shared:
         os.environ["MDP_SHARED_GPU"] = "1"
+    else:
+        # the host-only init (gloo, LOCAL_RANK kept): on a GPU host this child sees no device,
+        # so the case is the same one wherever the suite runs
+        os.environ.update(HIP_VISIBLE_DEVICES="", CUDA_VISIBLE_DEVICES="")
     from maddpg_amd.parallel import init_process_group_from_env
     w, r, local = init_process_group_from_env()
     t = torch.tensor([float(r + 1)])
@@ -220,10 +224,15 @@ def test_init_process_group_from_env(shared):
     ps = [ctx.Process(target=_env_init_worker, args=(r, 2, port, shared, q)) for r in range(2)]
     for p in ps:
         p.start()
-    got = sorted(q.get(timeout=120) for _ in ps)
-    for p in ps:
-        p.join(timeout=60)
-        assert p.exitcode == 0
+    try:
+        got = sorted(q.get(timeout=120) for _ in ps)
+        for p in ps:
+            p.join(timeout=60)
+            assert p.exitcode == 0
+    finally:
+        for p in ps:        # a rank whose peer died must not outlive the test waiting for it
+            if p.is_alive():
+                p.terminate()
     assert [g[0] for g in got] == [0, 1] and all(g[1] == 2 for g in got)
     assert all(g[3] == "gloo" and g[4] == 3.0 for g in got)
     assert [g[2] for g in got] == ([0, 0] if shared else [0, 1])

@@ -7,7 +7,7 @@ set -e
 O=gpurun_out/${1:-ablib}; mkdir -p $O
 N=${2:-3}
 L=${3:-maddpg_amd/libmaddpg_hip_ref.so}
-B="python3 bench.py --no-cpu-baseline --no-throughput-figure --no-gather-stage --no-configs2 --steps 30 --warmup 5 ${4:-}"
+B="python3 bench.py --full --no-cpu-baseline --no-throughput-figure --no-gather-stage --no-configs2 --steps 30 --warmup 5 ${4:-}"
 for i in $(seq 1 $N); do
   timeout -k 10 150 $B > $O/base$i.json 2> $O/base$i.err
   MDP_LIB=$L timeout -k 10 150 $B > $O/ref$i.json 2> $O/ref$i.err

@@ -4,7 +4,7 @@
 set -e
 O=gpurun_out/${1:-ab}; mkdir -p $O
 V=${2:?variant library}
-B="python3 bench.py --no-cpu-baseline --no-throughput-figure --steps 30 --warmup 5"
+B="python3 bench.py --full --no-cpu-baseline --no-throughput-figure --steps 30 --warmup 5"
 for i in 1 2 3; do
   timeout -k 10 150 $B > $O/base$i.json 2> $O/base$i.err
   MDP_LIB=$V timeout -k 10 150 $B > $O/var$i.json 2> $O/var$i.err

@@ -15,7 +15,7 @@ run() {  # name nproc env-assignment [bench args...]
   local name=$1 np=$2 ev=$3; shift 3
   env $ev timeout -k 10 240 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node $np \
       --master-addr 127.0.0.1 --master-port $((29600 + RANDOM % 200)) \
-      bench.py --gpus $np --steps 10 --warmup 2 "$@" > $O/$name.json 2> $O/$name.err
+      bench.py --full --gpus $np --steps 10 --warmup 2 "$@" > $O/$name.json 2> $O/$name.err
   echo "$name: $(tail -c 400 $O/$name.json)"
 }
 run xgmi2 2 MDP_DP_XGMI=1
@@ -23,7 +23,7 @@ run xgmi4 4 MDP_DP_XGMI=1 --no-throughput-figure
 run torchdist2 2 MDP_NATIVE_DP=0
 # 8 ranks (7 peers per exchange, MDP_XCH_MAXW filled) launched by bench.py itself
 # (--gpus 8 without torchrun's environment), small E per rank
-env MDP_DP_XGMI=1 timeout -k 10 300 python3 bench.py --gpus 8 --num-envs 512 --steps 5 --warmup 2 \
+env MDP_DP_XGMI=1 timeout -k 10 300 python3 bench.py --full --gpus 8 --num-envs 512 --steps 5 --warmup 2 \
     --no-throughput-figure > $O/xgmi8.json 2> $O/xgmi8.err
 echo "xgmi8: $(tail -c 400 $O/xgmi8.json)"
 # configs[4]'s topology (general H=128 kernels), 2 ranks over xGMI

@@ -84,6 +84,13 @@ def parse_args(argv=None):
     parser.add_argument("--update-mode", choices=["strict", "throughput"], default="strict",
                         help="strict: the reference's update order; throughput: every agent's gradients from "
                              "the round-start parameters, then every optimizer step (SURVEY 8e, single GPU)")
+    parser.add_argument("--prioritized-replay", action="store_true", default=False,
+                        help="device-side prioritized experience replay (the reference's "
+                             "prioritized_replay_buffer.py; one sum tree per agent, strict mode, one GPU)")
+    parser.add_argument("--per-alpha", type=float, default=0.6, help="priority exponent (prioritized_replay_buffer.py:149)")
+    parser.add_argument("--per-beta0", type=float, default=0.4, help="initial importance-sampling exponent (:150)")
+    parser.add_argument("--per-beta-inc", type=float, default=0.001, help="beta increment per sample call (:151)")
+    parser.add_argument("--per-eps", type=float, default=0.01, help="added to |TD error| before the clip (:148)")
     return parser.parse_args(argv)
 
 
@@ -209,6 +216,19 @@ def train(arglist):
     world, rank, local = init_process_group_from_env()
     if torch.cuda.is_available():
         torch.cuda.set_device(local)
+    from maddpg_amd._lib import MdpError
+    from maddpg_amd.common.tf_util import per_kwargs
+    per = per_kwargs(arglist)
+    try:
+        runner = _make_runner(arglist, VecRunner, world, rank, per)
+    except MdpError as e:      # e.g. prioritized replay with throughput mode or several GPUs
+        if not per:
+            raise
+        raise SystemExit(str(e))
+    return _train(arglist, runner, exp_name, world, rank)
+
+
+def _make_runner(arglist, VecRunner, world, rank, per):
     runner = VecRunner(arglist.scenario, arglist.num_envs, n_agents=arglist.num_agents,
                        scenario_adversaries=arglist.scenario_adversaries,
                        num_adversaries=arglist.num_adversaries, good_policy=arglist.good_policy,
@@ -219,9 +239,14 @@ def train(arglist):
                        tau=arglist.tau, grad_clip=arglist.grad_clip, actor_reg=arglist.actor_reg,
                        capacity=arglist.buffer_size,
                        # the learning-curve windows of one terminal step span <= save_rate + E episodes
-                       episode_log_rows=max(4096, 4 * arglist.num_envs, arglist.save_rate + 2 * arglist.num_envs))
+                       episode_log_rows=max(4096, 4 * arglist.num_envs, arglist.save_rate + 2 * arglist.num_envs),
+                       **per)
     if arglist.update_mode != "strict":
         runner.eng.set_update_mode(arglist.update_mode)
+    return runner
+
+
+def _train(arglist, runner, exp_name, world, rank):
     n = runner.n
     num_adversaries = min(n, arglist.num_adversaries)
     say = (lambda *a: print(*a, flush=True)) if rank == 0 else (lambda *a: None)

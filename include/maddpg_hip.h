@@ -142,6 +142,12 @@ int mdp_buffer_put_agent(mdp_handle* h, int32_t agent, const int64_t* pos_dev,
                          const float* cols_dev, int64_t rows);
 /* host-tracked ring state after put_agent (len/next are per agent in the reference) */
 int mdp_buffer_set_len(mdp_handle* h, int64_t len, int64_t next_idx);
+/* the same with the count of rows the host ever added to the ring (monotone).
+ * Prioritized replay resets the priorities of exactly the rows added since the
+ * previous call, however often the ring wrapped meanwhile; mdp_buffer_set_len
+ * can only infer them from the move of the head (fewer than `capacity` rows
+ * between two calls).  Without prioritized replay it is mdp_buffer_set_len. */
+int mdp_buffer_set_ring(mdp_handle* h, int64_t len, int64_t next_idx, int64_t rows_total);
 /* random.seed(seed) on the device MT19937 (CPython init_by_array) */
 int mdp_seed_py_random(mdp_handle* h, uint64_t seed);
 /* random.setstate/getstate: 624 words + position (random.getstate()[1]) */
@@ -318,12 +324,85 @@ int mdp_env_step_bench(mdp_handle* h, float* info_dev);
 int64_t mdp_episode_count(mdp_handle* h);
 int mdp_episode_log(mdp_handle* h, int64_t first, int64_t n, float* out_host);
 
+/* ---- prioritized replay (opt-in; the reference's unused second buffer,
+ * maddpg/trainer/prioritized_replay_buffer.py, after Schaul et al. 2016) -----
+ * Proportional prioritization on the device, one sum tree per agent driven by
+ * that agent's own critic TD error (DESIGN.md "Prioritized replay" holds the
+ * semantics and the departures from the reference module):
+ *   priority of a trained row   min(|q - y| + eps, abs_err_upper) ** alpha (fp32)
+ *   priority of a written row   abs_err_upper ** alpha (every ring write resets it)
+ *   tree                        complete binary tree over P = 2^k >= capacity
+ *                               leaves; node = {sum, min} fp32, parent.sum =
+ *                               fl32(left.sum + right.sum), parent.min = min;
+ *                               an unfilled leaf is {0, +inf}.  Ancestors are
+ *                               recomputed from their children (no deltas, no
+ *                               float atomics): the tree is a pure function of
+ *                               its leaves, graph replay == eager
+ *   sampling of B rows          seg = total / B, v_i = (i + u_i) * seg, descent:
+ *                               right (v -= left.sum) iff v >= left.sum and
+ *                               right.sum > 0.  u_i injected or Philox word 0 of
+ *                               counter (i, samples drawn by this agent,
+ *                               0x50000 | agent, 0), key = cfg.seed, through u01
+ *   IS weight                   beta <- min(1, beta + beta_inc) first, then
+ *                               w_i = (p_i / p_min) ** -beta, p_min = root.min
+ *   critic step                 loss mean_b(w_b (q_b - y_b)^2); the actor step is
+ *                               unweighted
+ * State lives in a SECOND caller-allocated device buffer of mdp_per_bytes(cfg)
+ * bytes (the arena and mdp_arena_bytes are unchanged): the ring-sync cursor,
+ * per-agent beta and sample counter, per-agent index / weight / |TD error|
+ * slots [n][B] and the trees.  It is not checkpointed (nor is the replay ring).
+ * mdp_per_enable comes before the handle's first update / train call (captured
+ * graphs never go stale); afterwards, with the defaults of the reference module
+ * alpha 0.6, beta0 0.4, beta_inc 0.001, eps 0.01, abs_err_upper 1:
+ *   mdp_update(idx_dev == NULL) draws the rows from that agent's tree; with
+ *   idx_dev it takes those rows and their weights from the tree (beta advances
+ *   the same way); the rows' priorities are written back after the critic step.
+ *   mdp_update_round / mdp_train_step / mdp_train_steps do the same per round,
+ *   eagerly and captured: ring sync, every agent's draw (one launch), the strict
+ *   round, every agent's write-back (one launch).  No MT19937 index draw runs.
+ * Refused with a message: throughput mode (either call order), any
+ * data-parallel wiring (mdp_dp_init, mdp_dp_xgmi_*, world_size > 1), the phase
+ * entry point mdp_critic_grad. */
+int64_t mdp_per_bytes(const mdp_config* cfg);
+int mdp_per_enable(mdp_handle* h, void* buf_dev, int64_t bytes, float alpha, float beta0, float beta_inc,
+                   float eps, float abs_err_upper);
+/* `count` rows of agent's tree (ring positions, not tree indices) and their IS
+ * weights; u_dev: [count] injected uniforms in [0, 1) or NULL (device Philox).
+ * Advances the agent's beta and sample counter on the device.  A row without a
+ * priority -- an unfilled position among the rows given to mdp_update, or a
+ * priority the caller set to 0 (such a leaf is {0, +inf} like an unfilled one:
+ * never drawn, not part of p_min) -- gets weight 0 (it takes no part in the
+ * critic loss) instead of inf / NaN; the draw itself needs total > 0, so keep
+ * at least one priority positive. */
+int mdp_per_sample(mdp_handle* h, int32_t agent, int32_t count, const float* u_dev, int32_t* idx_out_dev,
+                   float* w_out_dev);
+/* leaves of ring positions pos_dev [count] <- p_dev (raw priorities), or <-
+ * min(abs_err + eps, abs_err_upper) ** alpha; ancestors repaired.  A position
+ * repeated in one call gets the largest of its values (a row drawn twice has
+ * its TD target sampled twice), whatever the order; priorities are >= 0;
+ * positions outside the filled ring (< 0, >= the ring length) are ignored. */
+int mdp_per_set_priorities(mdp_handle* h, int32_t agent, const int32_t* pos_dev, const float* p_dev, int32_t count);
+int mdp_per_update_errors(mdp_handle* h, int32_t agent, const int32_t* pos_dev, const float* abs_err_dev,
+                          int32_t count);
+/* byte offsets inside the PER buffer of agent's slots of its last update:
+ * out3 = {indices int32 [B], IS weights fp32 [B], |TD errors| fp32 [B]} */
+int mdp_per_slots(mdp_handle* h, int32_t agent, int64_t out3[3]);
+/* nodes of one tree (2 P; -1 without PER); mdp_per_get_tree copies agent's
+ * [2 P][2] floats {sum, min} (node 0 unused and zero, node 1 the root, node
+ * P + i ring position i) after bringing the tree up to date with the ring */
+int64_t mdp_per_tree_nodes(const mdp_handle* h);
+int mdp_per_get_tree(mdp_handle* h, int32_t agent, float* nodes_host);
+/* out5 = {beta, total (root.sum), p_min (root.min), ring rows synced into the
+ * trees so far, sample calls of this agent}; synchronises */
+int mdp_per_info(mdp_handle* h, int32_t agent, double out5[5]);
+
 /* ---- profiling: HIP events bracketing every launch of one kernel kind -- */
 enum mdp_kernel_kind {
     MDP_K_INDEX = 0, MDP_K_GATHER = 1, MDP_K_CRITIC_GRAD = 2, MDP_K_ACTOR_GRAD = 3,
     MDP_K_APPLY = 4, MDP_K_ROLLOUT = 5, MDP_K_REDUCE = 6, MDP_K_REDUCE_APPLY = 7,
     MDP_K_ALLREDUCE = 8,   /* the RCCL data-parallel all-reduces (not a kernel of this library) */
-    MDP_K_COUNT = 9
+    MDP_K_PER_SYNC = 9, MDP_K_PER_SAMPLE = 10, MDP_K_PER_UPDATE = 11,   /* prioritized replay (mdp_per.hip) */
+    MDP_K_COUNT = 12
 };
 int mdp_prof_enable(mdp_handle* h, int32_t kind, int32_t on);
 /* which grad kernels serve `agent`: 1 = register-resident k_*_grad_r (H = 64

@@ -31,6 +31,8 @@ REGION = {"theta": 0, "target": 1, "adam_m": 2, "adam_v": 3, "grad": 4, "replay"
           "stats": 7, "env": 8, "eplog": 9, "beta": 10, "slab": 11, "ctl": 12}
 KERNEL = {"index": 0, "gather": 1, "critic_grad": 2, "actor_grad": 3, "apply": 4, "rollout": 5,
           "reduce": 6, "reduce_apply": 7, "allreduce": 8}
+# the prioritized-replay kernels (mdp_per.hip), timed only when asked for by name
+KERNEL_PER = {"per_sync": 9, "per_sample": 10, "per_update": 11}
 
 
 class MdpConfig(ctypes.Structure):
@@ -95,6 +97,7 @@ SIGNATURES = {
     "mdp_buffer_add_rows": (ctypes.c_int, [_P, _P, _I64]),
     "mdp_buffer_put_agent": (ctypes.c_int, [_P, _I32, _P, _P, _I64]),
     "mdp_buffer_set_len": (ctypes.c_int, [_P, _I64, _I64]),
+    "mdp_buffer_set_ring": (ctypes.c_int, [_P, _I64, _I64, _I64]),
     "mdp_seed_py_random": (ctypes.c_int, [_P, ctypes.c_uint64]),
     "mdp_set_rng_state": (ctypes.c_int, [_P, _U32P]),
     "mdp_get_rng_state": (ctypes.c_int, [_P, _U32P]),
@@ -138,6 +141,16 @@ SIGNATURES = {
     "mdp_update_all": (ctypes.c_int, [_P, _P, _P, _P]),
     "mdp_episode_count": (_I64, [_P]),
     "mdp_episode_log": (ctypes.c_int, [_P, _I64, _I64, _F32P]),
+    "mdp_per_bytes": (_I64, [ctypes.POINTER(MdpConfig)]),
+    "mdp_per_enable": (ctypes.c_int, [_P, _P, _I64, ctypes.c_float, ctypes.c_float, ctypes.c_float,
+                                      ctypes.c_float, ctypes.c_float]),
+    "mdp_per_sample": (ctypes.c_int, [_P, _I32, _I32, _P, _P, _P]),
+    "mdp_per_set_priorities": (ctypes.c_int, [_P, _I32, _P, _P, _I32]),
+    "mdp_per_update_errors": (ctypes.c_int, [_P, _I32, _P, _P, _I32]),
+    "mdp_per_slots": (ctypes.c_int, [_P, _I32, ctypes.POINTER(_I64)]),
+    "mdp_per_tree_nodes": (_I64, [_P]),
+    "mdp_per_get_tree": (ctypes.c_int, [_P, _I32, _F32P]),
+    "mdp_per_info": (ctypes.c_int, [_P, _I32, _F64P]),
     "mdp_prof_enable": (ctypes.c_int, [_P, _I32, _I32]),
     "mdp_prof_read": (ctypes.c_int, [_P, _I32, _F64P, ctypes.POINTER(_I64)]),
 }

@@ -67,7 +67,7 @@ class Session:
         seed = self.seed if self.seed is not None else int(getattr(args, "seed", 0) or 0)
         self._engine = Engine(obs_dims, local_q, num_units=args.num_units, batch_size=args.batch_size,
                               max_episode_len=args.max_episode_len, capacity=int(1e6), lr=args.lr,
-                              gamma=args.gamma, seed=seed)
+                              gamma=args.gamma, seed=seed, **per_kwargs(args))
         self._engine.init_params(seed)
         return self._engine
 
@@ -144,3 +144,11 @@ def sync_rng_from_device(engine, st):
     """Write the device MT19937 state back into the module-global RNG."""
     new = engine.get_rng_state()
     random.setstate((st[0], tuple(int(x) for x in new), st[2]))
+
+
+def per_kwargs(args):
+    """Engine keywords of --prioritized-replay / --per-* (experiments/train.py); {} when off"""
+    if not getattr(args, "prioritized_replay", False):
+        return {}
+    return dict(prioritized=True, per_alpha=getattr(args, "per_alpha", 0.6), per_beta0=getattr(args, "per_beta0", 0.4),
+                per_beta_inc=getattr(args, "per_beta_inc", 0.001), per_eps=getattr(args, "per_eps", 0.01))

@@ -370,6 +370,19 @@ struct mdp_handle {
   uint32_t x_probe_ep = 0;
   bool p2p = false;
   bool xw_stats = false;              // stamp the exchange waits (mdp_dp_exchange_stats_enable)
+  // prioritized replay (mdp_per_enable): the caller's second device buffer --
+  // cursor, per-agent beta / sample counter, per-agent index / weight / |TD
+  // error| slots [n][B], one sum tree per agent
+  bool per = false;
+  bool trained = false;               // an update / train call was made (mdp_per_enable must precede it)
+  PerHdr* per_hdr = nullptr;
+  PerState* per_st = nullptr;
+  int32_t* per_idx = nullptr;
+  float *per_w = nullptr, *per_td = nullptr;
+  PerNode* per_trees = nullptr;
+  int64_t per_P = 0;
+  float per_alpha = 0.6f, per_beta0 = 0.4f, per_beta_inc = 0.001f, per_eps = 0.01f, per_upper = 1.0f;
+  int64_t per_host_total = 0;         // mdp_buffer_set_ring's rows_total at the last call
 };
 
 namespace {
@@ -618,6 +631,15 @@ CriticArgs critic_args(mdp_handle* h, int agent, const int32_t* idx, const float
   return a;
 }
 
+// prioritized replay: the critic step's arguments + this agent's weight / |TD error| slots
+CriticArgsPer per_critic_args(mdp_handle* h, const CriticArgs& a) {
+  CriticArgsPer p;
+  static_cast<CriticArgs&>(p) = a;
+  p.is_w = h->per_w + (int64_t)a.agent * h->cfg.batch_size;
+  p.td_out = h->per_td + (int64_t)a.agent * h->cfg.batch_size;
+  return p;
+}
+
 int do_critic_grad(mdp_handle* h, int agent, const int32_t* idx, const float* u_tgt, int32_t* pf_out = nullptr,
                    bool tp = false, bool apre = false, const float* u_act = nullptr, int post_prev = -1,
                    int pf_n = 0, bool shared = false) {
@@ -630,11 +652,18 @@ int do_critic_grad(mdp_handle* h, int agent, const int32_t* idx, const float* u_
     }
     if (apre) a.apre = h->apre;
     if (post_prev >= 0) a.cpre = h->cpre;
-    HIPCHK(h, mdp_launch_critic_grad_r(a, lds_critic_r_bytes(h->L.topo, agent), h->stream));
+    if (h->per)
+      HIPCHK(h, mdp_launch_critic_grad_r_per(per_critic_args(h, a), lds_critic_r_bytes(h->L.topo, agent), h->stream));
+    else
+      HIPCHK(h, mdp_launch_critic_grad_r(a, lds_critic_r_bytes(h->L.topo, agent), h->stream));
     return 0;
   }
   if (lds_critic_bytes(h->L.topo, a.group) > MDP_LDS_BUDGET) return fail(h, "critic step does not fit in LDS");
-  HIPCHK(h, mdp_launch_critic_grad(a, h->L.topo.H, lds_critic_bytes(h->L.topo, a.group), h->stream));
+  if (h->per && !tp)
+    HIPCHK(h, mdp_launch_critic_grad_per(per_critic_args(h, a), h->L.topo.H, lds_critic_bytes(h->L.topo, a.group),
+                                         h->stream));
+  else
+    HIPCHK(h, mdp_launch_critic_grad(a, h->L.topo.H, lds_critic_bytes(h->L.topo, a.group), h->stream));
   return 0;
 }
 
@@ -1276,6 +1305,98 @@ int set_ring(mdp_handle* h, int64_t len, int64_t next) {
   return 0;
 }
 
+// ---- prioritized replay: layout of the PER buffer and the three launches
+struct PerLayout {
+  int64_t P = 1, hdr = 0, st = 0, idx = 0, w = 0, td = 0, trees = 0, total = 0;
+};
+PerLayout per_layout(const mdp_config& c) {
+  PerLayout p;
+  while (p.P < c.capacity) p.P <<= 1;
+  const int64_t nb = 4 * (int64_t)c.n_agents * c.batch_size;
+  int64_t o = 0;
+  p.hdr = o;
+  o += a256(sizeof(PerHdr));
+  p.st = o;
+  o += a256(sizeof(PerState) * MDP_MAX_AGENTS);
+  p.idx = o;
+  o += a256(nb);
+  p.w = o;
+  o += a256(nb);
+  p.td = o;
+  o += a256(nb);
+  p.trees = o;
+  o += (int64_t)c.n_agents * 2 * p.P * (int64_t)sizeof(PerNode);
+  p.total = o;
+  return p;
+}
+
+// bring every agent's tree up to date with the ring (host_rows: rows the host
+// wrote since the last sync; reset: rebuild every leaf from the ring length)
+int per_sync(mdp_handle* h, int64_t host_rows, bool reset) {
+  PerSyncArgs a;
+  a.ctl = h->ctl;
+  a.hdr = h->per_hdr;
+  a.trees = h->per_trees;
+  a.tree_stride = 2 * h->per_P;
+  a.P = h->per_P;
+  a.cap = h->cfg.capacity;
+  a.E = h->cfg.num_envs;
+  a.host_rows = host_rows;
+  a.reset = reset ? 1 : 0;
+  a.upper = h->per_upper;
+  a.alpha = h->per_alpha;
+  ProfScope p(h, MDP_K_PER_SYNC);
+  HIPCHK(h, mdp_launch_per_sync(a, h->cfg.n_agents, h->stream));
+  return 0;
+}
+
+// `count` rows of agents [agent0, agent0 + agents): the stratified descent (u:
+// injected uniforms, one agent) or the given rows idx_in; outputs `stride` apart
+int per_sample(mdp_handle* h, int agent0, int agents, int count, const float* u, const int32_t* idx_in,
+               int32_t* idx_out, float* w_out, int64_t stride) {
+  PerSampleArgs a;
+  a.trees = h->per_trees + (int64_t)agent0 * 2 * h->per_P;
+  a.tree_stride = 2 * h->per_P;
+  a.P = h->per_P;
+  a.cap = h->cfg.capacity;
+  a.st = h->per_st + agent0;
+  a.agent0 = agent0;
+  a.count = count;
+  a.u = u;
+  a.idx_in = idx_in;
+  a.idx_out = idx_out;
+  a.w_out = w_out;
+  a.stride = stride;
+  a.seed = h->cfg.seed;
+  a.beta_inc = h->per_beta_inc;
+  ProfScope p(h, MDP_K_PER_SAMPLE);
+  HIPCHK(h, mdp_launch_per_sample(a, agents, h->stream));
+  return 0;
+}
+
+int per_update(mdp_handle* h, int agent0, int agents, int count, const int32_t* pos, const float* val,
+               int64_t stride, bool from_err) {
+  PerUpdateArgs a;
+  a.trees = h->per_trees + (int64_t)agent0 * 2 * h->per_P;
+  a.tree_stride = 2 * h->per_P;
+  a.P = h->per_P;
+  a.cap = h->cfg.capacity;
+  a.count = count;
+  a.ctl = h->ctl;
+  a.pos = pos;
+  a.val = val;
+  a.stride = stride;
+  a.from_err = from_err ? 1 : 0;
+  a.eps = h->per_eps;
+  a.upper = h->per_upper;
+  a.alpha = h->per_alpha;
+  ProfScope p(h, MDP_K_PER_UPDATE);
+  HIPCHK(h, mdp_launch_per_update(a, agents, h->stream));
+  return 0;
+}
+
+const char* kPerNoDp = "prioritized replay runs on one GPU in strict mode: no data-parallel exchange";
+
 }  // namespace
 
 // ======================================================================= ABI
@@ -1556,7 +1677,9 @@ int mdp_buffer_add_rows(mdp_handle* h, const float* rows_dev, int64_t rows) {
   const int64_t start = (h->next + skip) % cap;
   HIPCHK(h, mdp_launch_put_rows(h->replay, h->L.topo.row_stride, cap, start,
                                 rows_dev + skip * h->L.topo.row_stride, rows - skip, h->stream));
-  return set_ring(h, std::min(cap, h->len + rows), (h->next + rows) % cap);
+  const int rc = set_ring(h, std::min(cap, h->len + rows), (h->next + rows) % cap);
+  if (rc || !h->per) return rc;
+  return per_sync(h, rows, false);  // the new rows' leaves
 }
 
 int mdp_buffer_put_agent(mdp_handle* h, int32_t agent, const int64_t* pos_dev, const float* cols_dev, int64_t rows) {
@@ -1573,7 +1696,32 @@ int mdp_buffer_set_len(mdp_handle* h, int64_t len, int64_t next_idx) {
   MDP_NEED(h);
   if (len < 0 || len > h->cfg.capacity || next_idx < 0 || next_idx >= h->cfg.capacity)
     return fail(h, "ring state out of range");
-  return set_ring(h, len, next_idx);
+  if (!h->per) return set_ring(h, len, next_idx);
+  // prioritized replay: a plain advance of the head makes those rows new; any
+  // other change of the ring state rebuilds every leaf from the new length
+  const int64_t cap = h->cfg.capacity, rows = (next_idx - h->next + cap) % cap;
+  const bool same = rows == 0 && len == h->len;
+  const bool advance = rows > 0 && len == std::min(cap, h->len + rows);
+  const int rc = set_ring(h, len, next_idx);
+  if (rc || same) return rc;
+  return per_sync(h, advance ? rows : 0, !advance);
+}
+
+int mdp_buffer_set_ring(mdp_handle* h, int64_t len, int64_t next_idx, int64_t rows_total) {
+  MDP_NEED(h);
+  if (len < 0 || len > h->cfg.capacity || next_idx < 0 || next_idx >= h->cfg.capacity || rows_total < 0)
+    return fail(h, "ring state out of range");
+  if (!h->per) return set_ring(h, len, next_idx);
+  // prioritized replay: exactly the rows added since the last call are new (a
+  // count, not a difference of ring heads: it survives any number of wraps; at
+  // least `capacity` of them reset every filled leaf).  A state that does not
+  // follow from the previous one by that many appends rebuilds every leaf.
+  const int64_t cap = h->cfg.capacity, rows = rows_total - h->per_host_total;
+  const bool follows = rows >= 0 && next_idx == (h->next + rows) % cap && len == std::min(cap, h->len + rows);
+  h->per_host_total = rows_total;
+  const int rc = set_ring(h, len, next_idx);
+  if (rc || (follows && rows == 0)) return rc;
+  return per_sync(h, follows ? rows : 0, !follows);
 }
 
 int mdp_seed_py_random(mdp_handle* h, uint64_t seed) {
@@ -1706,6 +1854,18 @@ int mdp_update(mdp_handle* h, int32_t agent, const int32_t* idx_dev, const float
   MDP_DEV(h, idx_dev, 4 * B, "mdp_update", true);
   MDP_DEV(h, u_tgt_dev, 4 * n * B * MDP_ACT_DIM, "mdp_update", true);
   MDP_DEV(h, u_act_dev, 4 * B * MDP_ACT_DIM, "mdp_update", true);
+  h->trained = true;
+  if (h->per) {
+    // this agent's tree gives the rows (or, for given rows, their weights: beta
+    // advances the same way); the critic step's |TD errors| go back as priorities
+    if (h->len <= 0) return fail(h, "update on an empty replay buffer");
+    int32_t* slot = h->per_idx + agent * B;
+    int rc;
+    if ((rc = per_sync(h, 0, false))) return rc;
+    if ((rc = per_sample(h, agent, 1, (int)B, nullptr, idx_dev, slot, h->per_w + agent * B, 0))) return rc;
+    if ((rc = do_update(h, agent, slot, u_tgt_dev, u_act_dev))) return rc;
+    return per_update(h, agent, 1, (int)B, slot, h->per_td + agent * B, 0, true);
+  }
   const int32_t* idx = idx_dev;
   if (!idx) {
     int32_t* slot = h->index + (int64_t)agent * h->cfg.batch_size;
@@ -1809,8 +1969,25 @@ static bool prefetch_ok(const mdp_handle* h) {
   return !h->general_grads && grads_r_ok(h->L.topo, 0) && h->cfg.n_agents * h->cfg.batch_size <= 4096;
 }
 
+// One round with prioritized replay: the ring sync (sync: the first round
+// after ring writes), every agent's stratified draw + IS weights in one launch,
+// the strict round on those rows (no MT19937 draw anywhere; the apre / cpre
+// hand-offs between the agents stay: every index of the round exists by now),
+// every agent's priority write-back in one launch.  Drawing at the round's
+// start equals the per-agent order: agent j's tree changes only by its own
+// previous write-back and by ring writes, both before the round.
+static int per_round_launches(mdp_handle* h, bool sync) {
+  const int n = h->cfg.n_agents, B = h->cfg.batch_size;
+  int rc;
+  if (sync && (rc = per_sync(h, 0, false))) return rc;
+  if ((rc = per_sample(h, 0, n, B, nullptr, nullptr, h->per_idx, h->per_w, B))) return rc;
+  if ((rc = round_updates(h, h->per_idx))) return rc;
+  return per_update(h, 0, n, B, h->per_idx, h->per_td, B, true);
+}
+
 static int round_launches(mdp_handle* h) {
   const int n = h->cfg.n_agents, B = h->cfg.batch_size;
+  if (h->per) return per_round_launches(h, true);
   int rc = launch_make_index(h, n * B, h->index);
   if (rc) return rc;
   return round_updates(h, h->index);
@@ -1829,6 +2006,7 @@ static bool any_prof(const mdp_handle* h) {
 int mdp_update_round(mdp_handle* h) {
   MDP_NEED(h);
   if (h->len <= 0) return fail(h, "update round on an empty replay buffer");
+  h->trained = true;
   if (!h->graphs || any_prof(h) || h->eager_rounds < 1) {
     ++h->eager_rounds;  // the first round runs eagerly (one-time kernel attribute setup)
     return round_launches(h);
@@ -1867,6 +2045,7 @@ int mdp_dp_unique_id(uint8_t* out128) {
 
 int mdp_dp_init(mdp_handle* h, const uint8_t* id128, int32_t world, int32_t rank) {
   if (unusable(h) || !id128) return -1;
+  if (h->per) return fail(h, kPerNoDp);
   if (h->update_mode != 0) return fail(h, "join data parallelism before choosing the throughput mode");
   if (h->p2p || h->xbuf) return fail(h, "mdp_dp_init: the xGMI exchange is already set up");
   if (!rccl().ok) return fail(h, "librccl.so.1 could not be loaded");
@@ -1904,6 +2083,7 @@ static void drop_graphs(mdp_handle* h);
 
 int mdp_dp_xgmi_open(mdp_handle* h, int32_t world, int32_t rank, uint8_t* handle_out) {
   if (unusable(h) || !handle_out) return -1;
+  if (h->per) return fail(h, kPerNoDp);
   if (h->update_mode != 0) return fail(h, "join data parallelism before choosing the throughput mode");
   if (h->comm) return fail(h, "mdp_dp_xgmi_open: an RCCL communicator is already set up");
   if (h->xbuf) return fail(h, "mdp_dp_xgmi_open: already open");
@@ -1977,6 +2157,7 @@ int mdp_dp_xgmi_probe(mdp_handle* h, int32_t* mismatches) {
 int mdp_dp_xgmi_enable(mdp_handle* h) {
   if (unusable(h)) return -1;
   if (!h->xd_dev) return fail(h, "mdp_dp_xgmi_enable: not connected");
+  if (h->per) return fail(h, kPerNoDp);
   if (h->update_mode != 0) return fail(h, "join data parallelism before choosing the throughput mode");
   HIPCHK(h, hipStreamSynchronize(h->stream));
   h->p2p = true;
@@ -2064,6 +2245,7 @@ int mdp_set_update_mode(mdp_handle* h, int32_t mode) {
   if (unusable(h)) return -1;
   if (mode != 0 && mode != 1) return fail(h, "update mode must be 0 (strict) or 1 (throughput)");
   if (mode == 1) {
+    if (h->per) return fail(h, "prioritized replay needs the strict update mode (throughput mode is not supported)");
     if (!tp_ok(h)) return fail(h, "throughput mode needs the fused optimizer step for every net and <= 8 agents");
     HIPCHK(h, hipStreamSynchronize(h->stream));
     if (tp_setup(h)) return -1;
@@ -2079,6 +2261,7 @@ int mdp_set_update_mode(mdp_handle* h, int32_t mode) {
 int mdp_update_all(mdp_handle* h, const int32_t* idx_dev, const float* u_tgt_dev, const float* u_act_dev) {
   if (unusable(h)) return -1;
   if (h->update_mode != 1) return fail(h, "mdp_update_all: set throughput mode first");
+  h->trained = true;
   if (h->len <= 0) return fail(h, "update on an empty replay buffer");
   {
     const int64_t B = h->cfg.batch_size, n = h->cfg.n_agents;
@@ -2098,6 +2281,8 @@ int mdp_update_all(mdp_handle* h, const int32_t* idx_dev, const float* u_tgt_dev
 int mdp_critic_grad(mdp_handle* h, int32_t agent, const int32_t* idx_dev, const float* u_tgt_dev) {
   if (bad_agent(h, agent)) return -1;
   if (!idx_dev) return fail(h, "critic_grad needs indices");
+  if (h->per) return fail(h, "mdp_critic_grad: the phase entry points serve data parallelism; prioritized replay uses mdp_update");
+  h->trained = true;
   MDP_DEV(h, idx_dev, 4 * (int64_t)h->cfg.batch_size, "mdp_critic_grad", false);
   MDP_DEV(h, u_tgt_dev, 4 * (int64_t)h->cfg.n_agents * h->cfg.batch_size * MDP_ACT_DIM, "mdp_critic_grad", true);
   return do_critic_grad(h, agent, idx_dev, u_tgt_dev);
@@ -2229,6 +2414,11 @@ int mdp_env_step_bench(mdp_handle* h, float* info_dev) {
 // critical path for every round but the first
 static int step_launches(mdp_handle* h, int rounds) {
   const int nb = h->cfg.n_agents * h->cfg.batch_size;
+  if (h->per) {  // prioritized replay: no index prefetch in any launch
+    int rc = env_step_launch(h, nullptr, nullptr);
+    for (int r = 0; r < rounds && !rc; ++r) rc = per_round_launches(h, r == 0);
+    return rc;
+  }
   int32_t* slot[2] = {h->index, h->index + nb};
   // the critic-launch prefetch serves throughput mode only where its one critic
   // launch covers every agent (tp_fast); a mix of fast and general agents
@@ -2338,6 +2528,7 @@ int mdp_train_steps(mdp_handle* h, int32_t n, const int32_t* rounds, int32_t lau
   std::vector<int> ks(rounds, rounds + n);
   for (int k : ks)
     if (k < 0 || k > 64) return fail(h, "mdp_train_steps: rounds must be in [0, 64]");
+  h->trained = true;
   // steps without a round (replay below the gate, or fewer than train_every
   // transitions per step: E = 1 trains every 100th step) are their rollout
   // launch alone inside the group's graph
@@ -2373,6 +2564,7 @@ int mdp_train_step(mdp_handle* h, int32_t rounds) {
   if (need_env(h)) return -1;
   if (rounds < 0 || rounds > 64) return fail(h, "mdp_train_step: rounds must be in [0, 64]");
   if (rounds > 0 && h->len + h->cfg.num_envs <= 0) return fail(h, "update round on an empty replay buffer");
+  h->trained = true;
   // the index kernels read the ring length the rollout leaves (device Ctl); the
   // host mirror moves first so the empty-buffer guard sees the same state, and
   // moves back when the step could not be launched
@@ -2473,6 +2665,149 @@ int mdp_episode_log(mdp_handle* h, int64_t first, int64_t n, float* out) {
     done += span;
   }
   HIPCHK(h, hipStreamSynchronize(h->stream));
+  return 0;
+}
+
+// ------------------------------------------------------ prioritized replay
+int64_t mdp_per_bytes(const mdp_config* cfg) {
+  Layout L;
+  std::string err;
+  if (!build_layout(cfg, L, err)) return -1;
+  return per_layout(*cfg).total;
+}
+
+int mdp_per_enable(mdp_handle* h, void* buf_dev, int64_t bytes, float alpha, float beta0, float beta_inc, float eps,
+                   float abs_err_upper) {
+  MDP_NEED(h);
+  if (h->per) return fail(h, "mdp_per_enable: already enabled");
+  if (h->trained)
+    return fail(h, "mdp_per_enable: call it before the handle's first update or train call");
+  if (h->update_mode != 0)
+    return fail(h, "prioritized replay needs the strict update mode (throughput mode is not supported)");
+  if (h->comm || h->p2p || h->xbuf || h->cfg.world_size > 1) return fail(h, kPerNoDp);
+  if (!(alpha >= 0.f) || !(beta0 >= 0.f && beta0 <= 1.f) || !(beta_inc >= 0.f) || !(eps >= 0.f) ||
+      !(abs_err_upper > 0.f) || !std::isfinite(alpha) || !std::isfinite(beta_inc) || !std::isfinite(eps) ||
+      !std::isfinite(abs_err_upper))
+    return fail(h, "mdp_per_enable: need alpha >= 0, 0 <= beta0 <= 1, beta_inc >= 0, eps >= 0, abs_err_upper > 0");
+  const PerLayout pl = per_layout(h->cfg);
+  if (bytes < pl.total) return fail(h, "mdp_per_enable: buffer smaller than mdp_per_bytes");
+  MDP_DEV(h, buf_dev, pl.total, "mdp_per_enable", false);
+  char* b = (char*)buf_dev;
+  h->per_hdr = (PerHdr*)(b + pl.hdr);
+  h->per_st = (PerState*)(b + pl.st);
+  h->per_idx = (int32_t*)(b + pl.idx);
+  h->per_w = (float*)(b + pl.w);
+  h->per_td = (float*)(b + pl.td);
+  h->per_trees = (PerNode*)(b + pl.trees);
+  h->per_P = pl.P;
+  h->per_alpha = alpha;
+  h->per_beta0 = beta0;
+  h->per_beta_inc = beta_inc;
+  h->per_eps = eps;
+  h->per_upper = abs_err_upper;
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  HIPCHK(h, hipMemsetAsync(b, 0, pl.trees, h->stream));
+  PerState st[MDP_MAX_AGENTS];
+  std::memset(st, 0, sizeof(st));
+  for (int i = 0; i < h->cfg.n_agents; ++i) {
+    st[i].beta = beta0;
+    HIPCHK(h, hipMemsetAsync(h->per_trees + (int64_t)i * 2 * pl.P, 0, sizeof(PerNode), h->stream));  // node 0: unused
+  }
+  HIPCHK(h, hipMemcpyAsync(h->per_st, st, sizeof(st), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  h->per = true;
+  drop_graphs(h);  // graphs captured with the uniform draw
+  // every filled row starts at the new-row priority; the cursor at the ring's present state
+  if (per_sync(h, 0, true)) {
+    h->per = false;
+    return -1;
+  }
+  return 0;
+}
+
+static int need_per(mdp_handle* h, int32_t agent, const char* fn) {
+  if (bad_agent(h, agent)) return -1;
+  if (!h->per) return fail(h, (std::string(fn) + ": prioritized replay is not enabled (mdp_per_enable)").c_str());
+  return 0;
+}
+
+int mdp_per_sample(mdp_handle* h, int32_t agent, int32_t count, const float* u_dev, int32_t* idx_out_dev,
+                   float* w_out_dev) {
+  if (need_per(h, agent, "mdp_per_sample")) return -1;
+  if (count < 1 || count > (1 << 20)) return fail(h, "mdp_per_sample: count must be in [1, 2^20]");
+  if (h->len <= 0) return fail(h, "mdp_per_sample on an empty replay buffer");
+  MDP_DEV(h, u_dev, 4 * (int64_t)count, "mdp_per_sample", true);
+  MDP_DEV(h, idx_out_dev, 4 * (int64_t)count, "mdp_per_sample", false);
+  MDP_DEV(h, w_out_dev, 4 * (int64_t)count, "mdp_per_sample", false);
+  const int rc = per_sync(h, 0, false);
+  if (rc) return rc;
+  return per_sample(h, agent, 1, count, u_dev, nullptr, idx_out_dev, w_out_dev, 0);
+}
+
+static int per_write(mdp_handle* h, int32_t agent, const int32_t* pos_dev, const float* val_dev, int32_t count,
+                     bool from_err, const char* fn) {
+  if (need_per(h, agent, fn)) return -1;
+  if (count < 0 || count > (1 << 20)) return fail(h, (std::string(fn) + ": count must be in [0, 2^20]").c_str());
+  if (count == 0) return 0;
+  if (need_dev(h, pos_dev, 4 * (int64_t)count, fn, "pos_dev", false)) return -1;
+  if (need_dev(h, val_dev, 4 * (int64_t)count, fn, from_err ? "abs_err_dev" : "p_dev", false)) return -1;
+  const int rc = per_sync(h, 0, false);
+  if (rc) return rc;
+  return per_update(h, agent, 1, count, pos_dev, val_dev, 0, from_err);
+}
+
+int mdp_per_set_priorities(mdp_handle* h, int32_t agent, const int32_t* pos_dev, const float* p_dev, int32_t count) {
+  return per_write(h, agent, pos_dev, p_dev, count, false, "mdp_per_set_priorities");
+}
+
+int mdp_per_update_errors(mdp_handle* h, int32_t agent, const int32_t* pos_dev, const float* abs_err_dev,
+                          int32_t count) {
+  return per_write(h, agent, pos_dev, abs_err_dev, count, true, "mdp_per_update_errors");
+}
+
+int64_t mdp_per_tree_nodes(const mdp_handle* h) { return (unusable(h) || !h->per) ? -1 : 2 * h->per_P; }
+
+int mdp_per_slots(mdp_handle* h, int32_t agent, int64_t out3[3]) {
+  if (need_per(h, agent, "mdp_per_slots")) return -1;
+  if (!out3) return fail(h, "mdp_per_slots: out is null");
+  const PerLayout pl = per_layout(h->cfg);
+  const int64_t o = 4 * (int64_t)agent * h->cfg.batch_size;
+  out3[0] = pl.idx + o;
+  out3[1] = pl.w + o;
+  out3[2] = pl.td + o;
+  return 0;
+}
+
+int mdp_per_get_tree(mdp_handle* h, int32_t agent, float* nodes_host) {
+  if (need_per(h, agent, "mdp_per_get_tree")) return -1;
+  if (!nodes_host) return fail(h, "mdp_per_get_tree: nodes_host is null");
+  const int rc = per_sync(h, 0, false);
+  if (rc) return rc;
+  const int64_t nodes = 2 * h->per_P;
+  HIPCHK(h, hipMemcpyAsync(nodes_host, h->per_trees + agent * nodes, nodes * sizeof(PerNode), hipMemcpyDeviceToHost,
+                           h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  return 0;
+}
+
+int mdp_per_info(mdp_handle* h, int32_t agent, double out5[5]) {
+  if (need_per(h, agent, "mdp_per_info")) return -1;
+  if (!out5) return fail(h, "mdp_per_info: out is null");
+  const int rc = per_sync(h, 0, false);
+  if (rc) return rc;
+  PerState st;
+  PerHdr hd;
+  PerNode root;
+  HIPCHK(h, hipMemcpyAsync(&st, h->per_st + agent, sizeof(st), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipMemcpyAsync(&hd, h->per_hdr, sizeof(hd), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipMemcpyAsync(&root, h->per_trees + (int64_t)agent * 2 * h->per_P + 1, sizeof(root),
+                           hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  out5[0] = st.beta;
+  out5[1] = root.sum;
+  out5[2] = root.min;
+  out5[3] = (double)hd.rows_synced;
+  out5[4] = (double)st.samples;
   return 0;
 }
 

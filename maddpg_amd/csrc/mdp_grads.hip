@@ -350,8 +350,8 @@ static_assert(MDP_GEN_THREADS / 64 >= MDP_MAX_UNITS / 16, "one single-net layer 
 
 // blk: this workgroup's row tile (blockIdx.x, or its index inside the
 // critic half of a gradient-pair launch)
-template <int H>
-__device__ __forceinline__ void critic_body(const CriticArgs& a, const Topo& T, const int blk) {
+template <int H, bool PER = false, class A = CriticArgs>
+__device__ __forceinline__ void critic_body(const A& a, const Topo& T, const int blk) {
   // (no MDP_KARG_TOUCH here: at H = 128 it turned the kernel's 47 spilled
   // SGPRs into 91 spilled VGPRs)
   constexpr int NT = H / 16;
@@ -596,6 +596,12 @@ __device__ __forceinline__ void critic_body(const CriticArgs& a, const Topo& T, 
       const float diff = qv[lane * 8] - y;
       g = (2.0f * diff) * a.inv_b;
       s_l = (double)diff * (double)diff;
+      if constexpr (PER) {  // prioritized replay: the importance-sampling weight at the seed and in the loss
+        const float w = a.is_w[r0 + lane];
+        g = ((2.0f * diff) * w) * a.inv_b;
+        s_l = (double)w * s_l;
+        a.td_out[r0 + lane] = fabsf(diff);
+      }
       s_y = y64;
       s_r = rew;
       s_q = qn;
@@ -647,9 +653,10 @@ __device__ __forceinline__ void critic_body(const CriticArgs& a, const Topo& T, 
   MDP_STAMP(5);
 }
 
-template <int H>
-__global__ __launch_bounds__(MDP_GEN_THREADS) void k_critic_grad(CriticArgs a) {
-  critic_body<H>(a, a.topo, blockIdx.x);
+// PER: the prioritized-replay twin (A = CriticArgsPer), strict mode only
+template <int H, bool PER = false, class A = CriticArgs>
+__global__ __launch_bounds__(MDP_GEN_THREADS) void k_critic_grad(A a) {
+  critic_body<H, PER>(a, a.topo, blockIdx.x);
 }
 
 // AA: ActorArgs, or the Topo-less ActorArgsHead of a gradient-pair launch
@@ -936,6 +943,18 @@ hipError_t launch_critic(const CriticArgs& a, int lds, hipStream_t s) {
   return hipGetLastError();
 }
 template <int H>
+hipError_t launch_critic_per(const CriticArgsPer& a, int lds, hipStream_t s) {
+  static bool attr = false;
+  if (!attr) {
+    (void)hipFuncSetAttribute((const void*)k_critic_grad<H, true, CriticArgsPer>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                              MDP_LDS_BUDGET);
+    (void)hipGetLastError();
+    attr = true;
+  }
+  mdp_launch(k_critic_grad<H, true, CriticArgsPer>, dim3((a.B + MDP_R - 1) / MDP_R), dim3(MDP_GEN_THREADS), lds, s, a);
+  return hipGetLastError();
+}
+template <int H>
 hipError_t launch_actor(const ActorArgs& a, int lds, hipStream_t s) {
   static bool attr = false;
   if (!attr) {
@@ -976,6 +995,14 @@ hipError_t mdp_launch_critic_grad(const CriticArgs& a, int H, int lds_bytes, hip
     case 64: return launch_critic<64>(a, lds_bytes, s);
     case 128: return launch_critic<128>(a, lds_bytes, s);
     case 256: return launch_critic<256>(a, lds_bytes, s);
+    default: return hipErrorInvalidValue;
+  }
+}
+hipError_t mdp_launch_critic_grad_per(const CriticArgsPer& a, int H, int lds_bytes, hipStream_t s) {
+  switch (H) {
+    case 64: return launch_critic_per<64>(a, lds_bytes, s);
+    case 128: return launch_critic_per<128>(a, lds_bytes, s);
+    case 256: return launch_critic_per<256>(a, lds_bytes, s);
     default: return hipErrorInvalidValue;
   }
 }

@@ -528,7 +528,10 @@ __device__ __forceinline__ void critic_pre_tile(const ActorArgs& a, float* lds, 
 }
 }  // namespace
 
-__global__ __launch_bounds__(512) void k_critic_grad_r(CriticArgs a) {
+// PER: the prioritized-replay twin (A = CriticArgsPer: a.is_w / a.td_out); the
+// uniform kernel (A = CriticArgs) carries none of its code or arguments
+template <bool PER, class A>
+__global__ __launch_bounds__(512) void k_critic_grad_r(A a) {
   MDP_KARG_TOUCH("s"(a.agent), "s"(a.inv_b), "s"(a.pf_count), "s"(a.cpre_prev), "s"(a.topo.n), "s"(gridDim.x));
   BUD_BEGIN(0, a.agent, a.multi);
   MDP_WG_START(0);
@@ -928,6 +931,12 @@ __global__ __launch_bounds__(512) void k_critic_grad_r(CriticArgs a) {
         const float diff = qv[lane] - y;
         g = (2.0f * diff) * a.inv_b;
         s_l = (double)diff * (double)diff;
+        if constexpr (PER) {  // prioritized replay: the importance-sampling weight at the seed and in the loss
+          const float w = a.is_w[r0 + lane];
+          g = ((2.0f * diff) * w) * a.inv_b;
+          s_l = (double)w * s_l;
+          a.td_out[r0 + lane] = fabsf(diff);
+        }
         s_y = y64;
         s_r = rew;
         s_q = qnv;
@@ -987,6 +996,7 @@ __global__ __launch_bounds__(512) void k_critic_grad_r(CriticArgs a) {
   MDP_STAMP(10);
   MDP_WG_END(0);
 }
+
 
 __global__ __launch_bounds__(512) void k_actor_grad_r(ActorArgs a) {
   MDP_KARG_TOUCH("s"(a.agent), "s"(a.slab_stride), "s"(a.cpre_agent), "s"(a.topo.n), "s"(gridDim.x));
@@ -1255,7 +1265,14 @@ hipError_t mdp_launch_critic_grad_r(const CriticArgs& a, int lds_bytes, hipStrea
   static bool attr = false;
   const int per = (a.B + MDP_RW - 1) / MDP_RW;
   // grid: critic row tiles | actor-forward row tiles (a.apre) | the index draw (pf_count; last)
-  return launch_r(k_critic_grad_r, a, lds_bytes, s, attr, (a.apre ? per : 0) + (a.pf_count > 0 ? 1 : 0));
+  return launch_r(k_critic_grad_r<false, CriticArgs>, a, lds_bytes, s, attr,
+                  (a.apre ? per : 0) + (a.pf_count > 0 ? 1 : 0));
+}
+hipError_t mdp_launch_critic_grad_r_per(const CriticArgsPer& a, int lds_bytes, hipStream_t s) {
+  static bool attr = false;
+  const int per = (a.B + MDP_RW - 1) / MDP_RW;
+  return launch_r(k_critic_grad_r<true, CriticArgsPer>, a, lds_bytes, s, attr,
+                  (a.apre ? per : 0) + (a.pf_count > 0 ? 1 : 0));
 }
 hipError_t mdp_launch_actor_grad_r(const ActorArgs& a, int lds_bytes, hipStream_t s) {
   static bool attr = false;

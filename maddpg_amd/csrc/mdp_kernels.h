@@ -53,6 +53,16 @@ struct CriticArgs {
   int cpre_prev;
   Topo topo;
 };
+// prioritized replay (strict mode): the argument block of the critic kernels'
+// PER twins (k_critic_grad_r_per, k_critic_grad_per -- the same body with the
+// weight at the seed and in the loss).  The uniform kernels keep CriticArgs and
+// every instruction they had.  is_w [B] importance-sampling weights: the loss
+// is mean_b(w_b (q_b - y_b)^2), dL/dq_b = 2 w_b (q_b - y_b) / B; td_out [B]
+// receives |q_b - y_b|
+struct CriticArgsPer : CriticArgs {
+  const float* is_w;
+  float* td_out;
+};
 
 // precomputed critic-step work of one batch row (k_actor_grad_r's extra
 // workgroups -> k_critic_grad_r in critic_post mode):
@@ -193,6 +203,68 @@ struct FusedApplyArgs {
 inline int64_t mdp_ra_sync_bytes() {
   return (int64_t)MDP_MAX_AGENTS * 2 * 8 * 128 + (int64_t)MDP_MAX_AGENTS * 2 * 6 * MDP_RA_MAXCH * 16;
 }
+
+// ---- prioritized replay (mdp_per.hip): one sum tree per agent in the caller's
+// PER buffer.  A tree over P = 2^k >= capacity leaves is the heap array
+// node[2 P] of {sum, min}: node 1 the root, node P + i the leaf of ring
+// position i, node 0 unused; an unfilled leaf is {0, +inf}.
+#define MDP_PER_STREAM 0x50000u   // Philox stream of the stratified draw: 0x50000 | agent
+#define MDP_PER_TOP 2048          // nodes of the top levels k_per_sample keeps in LDS
+struct PerNode {
+  float sum, min;
+};
+struct PerHdr {                   // the sync's own cursor (device state: graphs stay argument-invariant)
+  int64_t seen_steps;             // Ctl::env_steps at the last sync
+  int64_t rows_synced;            // leaves reset by ring writes so far (mdp_per_info)
+  uint32_t ticket;
+  uint32_t pad[11];
+};
+struct PerState {                 // per agent
+  float beta;
+  uint32_t samples;               // sample calls so far: the draw's Philox counter
+  uint32_t ticket;
+  uint32_t pad[13];
+};
+struct PerSyncArgs {
+  const Ctl* ctl;
+  PerHdr* hdr;
+  PerNode* trees;
+  int64_t tree_stride;            // nodes per agent (2 P)
+  int64_t P, cap;
+  int E;                          // ring rows per env step
+  int64_t host_rows;              // rows the host wrote since the last sync (eager calls only)
+  int reset;                      // rebuild every leaf from the ring length
+  // a new row's priority is powf(upper, alpha) formed on the device, the very
+  // value k_per_update gives a row whose error reaches the clip
+  float upper, alpha;
+};
+struct PerSampleArgs {
+  const PerNode* trees;
+  int64_t tree_stride, P, cap;
+  PerState* st;                   // of the launch's first agent
+  int agent0, count;
+  const float* u;                 // [count] injected uniforms (one agent) or null: device Philox
+  const int32_t* idx_in;          // [count] rows given by the caller (weights only) or null: stratified descent
+  int32_t* idx_out;               // per agent `stride` apart
+  float* w_out;
+  int64_t stride;
+  uint64_t seed;
+  float beta_inc;
+};
+struct PerUpdateArgs {
+  PerNode* trees;
+  int64_t tree_stride, P, cap;
+  int count;
+  const Ctl* ctl;                 // positions at or beyond Ctl::len (unfilled) are ignored
+  const int32_t* pos;             // per agent `stride` apart
+  const float* val;               // priorities (from_err 0) or |TD errors| (from_err 1)
+  int64_t stride;
+  int from_err;
+  float eps, upper, alpha;
+};
+hipError_t mdp_launch_per_sync(const PerSyncArgs& a, int agents, hipStream_t s);
+hipError_t mdp_launch_per_sample(const PerSampleArgs& a, int agents, hipStream_t s);
+hipError_t mdp_launch_per_update(const PerUpdateArgs& a, int agents, hipStream_t s);
 
 struct RolloutArgs {
   Topo topo;
@@ -343,6 +415,8 @@ hipError_t mdp_launch_critic_grad(const CriticArgs& a, int H, int lds_bytes, hip
 hipError_t mdp_launch_actor_grad(const ActorArgs& a, int H, int lds_bytes, hipStream_t s);
 hipError_t mdp_launch_grad_pair(const GradPairArgs& a, int H, int lds_bytes, hipStream_t s);
 hipError_t mdp_launch_critic_grad_r(const CriticArgs& a, int lds_bytes, hipStream_t s);
+hipError_t mdp_launch_critic_grad_per(const CriticArgsPer& a, int H, int lds_bytes, hipStream_t s);
+hipError_t mdp_launch_critic_grad_r_per(const CriticArgsPer& a, int lds_bytes, hipStream_t s);
 hipError_t mdp_launch_actor_grad_r(const ActorArgs& a, int lds_bytes, hipStream_t s);
 hipError_t mdp_launch_rollout(const RolloutArgs& a, int H, int lds_bytes, hipStream_t s);
 hipError_t mdp_launch_eval(const EvalArgs& a, int H, int lds_bytes, hipStream_t s);

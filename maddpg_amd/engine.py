@@ -34,7 +34,9 @@ class Engine:
     def __init__(self, obs_dims, local_q=None, *, num_units=64, batch_size=1024, max_episode_len=25,
                  capacity=int(1e6), num_envs=0, scenario="none", num_adversaries=0, lr=1e-2,
                  gamma=0.95, tau=1e-2, grad_clip=0.5, actor_reg=1e-3, adam_b1=0.9, adam_b2=0.999,
-                 adam_eps=1e-8, seed=0, world_size=1, rank=0, device=None, episode_log_rows=0):
+                 adam_eps=1e-8, seed=0, world_size=1, rank=0, device=None, episode_log_rows=0,
+                 prioritized=False, per_alpha=0.6, per_beta0=0.4, per_beta_inc=0.001, per_eps=0.01,
+                 per_abs_err_upper=1.0):
         self.lib = _lib.load()
         if not torch.cuda.is_available():
             raise RuntimeError("maddpg_amd runs on a ROCm GPU only (no CPU fallback)")
@@ -104,6 +106,10 @@ class Engine:
                     self._c("mdp_tensor", i, net, t, ctypes.byref(ti))
                     infos.append((ti.offset, ti.rows, ti.cols, ti.dev_rows, ti.dev_cols))
                 self._tensors[(i, net)] = infos
+        self.prioritized = bool(prioritized)
+        self.per_buf = None
+        if self.prioritized:
+            self._per_enable(per_alpha, per_beta0, per_beta_inc, per_eps, per_abs_err_upper)
 
     # ------------------------------------------------------------ plumbing
     def _c(self, name, *args):
@@ -331,8 +337,13 @@ class Engine:
         self._c("mdp_buffer_put_agent", agent, self._ptr(pos), self._ptr(cols), pos.shape[0])
         self.sync_out()
 
-    def set_ring(self, length, next_idx):
-        self._c("mdp_buffer_set_len", int(length), int(next_idx))
+    def set_ring(self, length, next_idx, rows_total=None):
+        """host ring state to the device; rows_total: rows ever added (prioritized
+        replay then resets exactly the rows added since the last call)"""
+        if rows_total is None:
+            self._c("mdp_buffer_set_len", int(length), int(next_idx))
+        else:
+            self._c("mdp_buffer_set_ring", int(length), int(next_idx), int(rows_total))
 
     def seed_py_random(self, seed):
         self._c("mdp_seed_py_random", int(seed) & 0xFFFFFFFFFFFFFFFF)
@@ -363,6 +374,78 @@ class Engine:
         self._c("mdp_sample_rows", self._ptr(idx), idx.shape[0], self._ptr(out))
         self.sync_out()
         return out
+
+    # -------------------------------------------------- prioritized replay
+    def _per_enable(self, alpha, beta0, beta_inc, eps, upper):
+        """device-side prioritized replay (mdp_per_enable): one sum tree per agent in
+        a second device buffer; before the first update / train call"""
+        nbytes = self.lib.mdp_per_bytes(ctypes.byref(self.cfg))
+        if nbytes < 0:
+            raise ValueError("mdp_per_bytes refused the configuration")
+        with torch.cuda.device(self.device):
+            self.per_buf = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        try:
+            self._c("mdp_per_enable", self._ptr(self.per_buf), nbytes, float(alpha), float(beta0),
+                    float(beta_inc), float(eps), float(upper))
+        except _lib.MdpError:
+            self.per_buf = None
+            self.close()
+            raise
+        self.per_nodes = int(self.lib.mdp_per_tree_nodes(self.h))
+
+    def per_sample(self, agent, count, u=None):
+        """(positions int32 [count], IS weights float32 [count]) from agent's tree:
+        the stratified draw with injected uniforms u or the device Philox
+        (mdp_per_sample; advances the agent's beta and sample counter)"""
+        count = int(count)
+        self._sized("u", u, count)
+        u = None if u is None else u.to(self.device, torch.float32).contiguous()
+        idx = torch.empty(count, dtype=torch.int32, device=self.device)
+        w = torch.empty(count, dtype=torch.float32, device=self.device)
+        self.sync_in()
+        self._c("mdp_per_sample", int(agent), count, self._ptr(u), self._ptr(idx), self._ptr(w))
+        self._keep = (u, idx, w)
+        self.sync_out()
+        return idx, w
+
+    def _per_write(self, name, agent, pos, val):
+        pos = torch.as_tensor(pos).to(self.device, torch.int32).contiguous().reshape(-1)
+        val = torch.as_tensor(val).to(self.device, torch.float32).contiguous().reshape(-1)
+        self._sized("values", val, pos.numel())
+        self.sync_in()
+        self._c(name, int(agent), self._ptr(pos), self._ptr(val), pos.numel())
+        self._keep = (pos, val)
+        self.sync_out()
+
+    def per_set_priorities(self, agent, pos, p):
+        """leaves of ring positions pos <- raw priorities p (mdp_per_set_priorities)"""
+        self._per_write("mdp_per_set_priorities", agent, pos, p)
+
+    def per_update_errors(self, agent, pos, abs_err):
+        """leaves of pos <- min(|err| + eps, upper) ** alpha (mdp_per_update_errors)"""
+        self._per_write("mdp_per_update_errors", agent, pos, abs_err)
+
+    def per_tree(self, agent):
+        """agent's tree [2 P, 2] float32 {sum, min}: node 1 the root, node P + i ring
+        position i, brought up to date with the ring first (mdp_per_get_tree)"""
+        if not self.prioritized:
+            raise _lib.MdpError("per_tree: prioritized replay is not enabled")
+        out = np.empty((self.per_nodes, 2), np.float32)
+        self._c("mdp_per_get_tree", int(agent), _lib.fptr(out))
+        return out
+
+    def per_info(self, agent):
+        out = (ctypes.c_double * 5)()
+        self._c("mdp_per_info", int(agent), out)
+        return {"beta": np.float32(out[0]), "total": np.float32(out[1]), "p_min": np.float32(out[2]),
+                "rows_synced": int(out[3]), "samples": int(out[4])}
+
+    def per_slots(self, agent):
+        """(idx int32, weights, |TD errors|) views [B] of agent's slots of the last update"""
+        off = (ctypes.c_int64 * 3)()
+        self._c("mdp_per_slots", int(agent), off)
+        sl = lambda k, dt: self.per_buf[off[k]: off[k] + 4 * self.batch_size].view(dt)
+        return sl(0, torch.int32), sl(1, torch.float32), sl(2, torch.float32)
 
     # ------------------------------------------------------------ policies
     def act(self, agent, obs, target=False, u=None):
@@ -709,10 +792,14 @@ class Engine:
         return r[start * self.row_stride:(start + count) * self.row_stride].view(count, self.row_stride)
 
     # ---------------------------------------------------------- profiling
+    @staticmethod
+    def _kind(kind):
+        return _lib.KERNEL[kind] if kind in _lib.KERNEL else _lib.KERNEL_PER[kind]
+
     def prof_enable(self, kind, on=True):
-        self._c("mdp_prof_enable", _lib.KERNEL[kind], 1 if on else 0)
+        self._c("mdp_prof_enable", self._kind(kind), 1 if on else 0)
 
     def prof_read(self, kind):
         ms, n = ctypes.c_double(), ctypes.c_int64()
-        self._c("mdp_prof_read", _lib.KERNEL[kind], ctypes.byref(ms), ctypes.byref(n))
+        self._c("mdp_prof_read", self._kind(kind), ctypes.byref(ms), ctypes.byref(n))
         return ms.value, n.value

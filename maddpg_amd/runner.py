@@ -45,7 +45,8 @@ class VecRunner:
                  num_adversaries=0, good_policy="maddpg", adv_policy="maddpg", batch_size=1024,
                  num_units=64, lr=1e-2, gamma=0.95, max_episode_len=25, capacity=int(1e6), seed=0,
                  train_every=100, world_size=1, rank=0, device=None, episode_log_rows=0, tau=1e-2,
-                 grad_clip=0.5, actor_reg=1e-3):
+                 grad_clip=0.5, actor_reg=1e-3, prioritized=False, per_alpha=0.6, per_beta0=0.4,
+                 per_beta_inc=0.001, per_eps=0.01, per_abs_err_upper=1.0):
         sp = envs.spec(scenario, n_agents, scenario_adversaries)
         self.spec = sp
         n = sp.n_agents
@@ -56,7 +57,9 @@ class VecRunner:
                           scenario=scenario, num_adversaries=sp.num_adversaries, lr=lr, gamma=gamma,
                           tau=tau, grad_clip=grad_clip, actor_reg=actor_reg,
                           seed=seed * 1000003 + 17, world_size=world_size, rank=rank, device=device,
-                          episode_log_rows=episode_log_rows)
+                          episode_log_rows=episode_log_rows, prioritized=prioritized, per_alpha=per_alpha,
+                          per_beta0=per_beta0, per_beta_inc=per_beta_inc, per_eps=per_eps,
+                          per_abs_err_upper=per_abs_err_upper)
         self.eng.init_params(seed)                           # identical replicas on every rank
         self.eng.seed_py_random(seed + rank)                 # per-rank index stream
         self.eng.env_reset()

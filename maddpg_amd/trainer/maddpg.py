@@ -111,9 +111,17 @@ class MADDPGAgentTrainer(AgentTrainer):
                 raise RuntimeError("all agents of an update must share one session")
         eng = self._eng()
         self.session.flush()
-        idx = self.replay_buffer.make_index_device(self.args.batch_size)   # :167
-        self.replay_sample_index = idx
-        eng.update(self.agent_index, idx=idx)                           # :173-194
+        if eng.prioritized:
+            # --prioritized-replay: the rows come from this agent's sum tree on the
+            # device (no draw from the global ``random`` stream), the critic step is
+            # importance-weighted and writes the rows' priorities back
+            self.replay_buffer.sync_ring()
+            eng.update(self.agent_index)
+            self.replay_sample_index = eng.per_slots(self.agent_index)[0].clone()
+        else:
+            idx = self.replay_buffer.make_index_device(self.args.batch_size)   # :167
+            self.replay_sample_index = idx
+            eng.update(self.agent_index, idx=idx)                       # :173-194
         host, ev = eng.stats_future(self.agent_index)
         ev.synchronize()
         if self.session.check_nan:                                      # tf_util.py:366-368

@@ -29,6 +29,7 @@ class ReplayBuffer(object):
         self._maxsize = int(size)
         self._next_idx = 0
         self._len = 0
+        self._total = 0             # rows ever added (what prioritized replay counts new rows by)
         self._session = _session
         self._agent = _agent
         self._engine = None
@@ -57,6 +58,7 @@ class ReplayBuffer(object):
 
     def add(self, obs_t, action, reward, obs_tp1, done):
         self._pending.append((self._next_idx, obs_t, action, reward, obs_tp1, done))
+        self._total += 1
         if self._next_idx >= self._len:
             self._len += 1
         self._next_idx = (self._next_idx + 1) % self._maxsize
@@ -82,6 +84,15 @@ class ReplayBuffer(object):
         keep = np.sort(k - 1 - last)
         eng.put_agent(self._agent, torch.from_numpy(pos[keep]), torch.from_numpy(cols[keep]))
         self._pending = []
+
+    def sync_ring(self):
+        """staged rows and the host ring state (len, next) to the device"""
+        self.flush()
+        eng = self._eng()
+        if self._len == 0:
+            raise ValueError("replay buffer is empty")
+        eng.set_ring(self._len, self._next_idx % eng.capacity, self._total if eng.prioritized else None)
+        return eng
 
     # ------------------------------------------------------------ indices
     def make_index_device(self, batch_size):

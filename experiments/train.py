@@ -162,6 +162,9 @@ def benchmark(arglist, runner, exp_name, rank):
     E, L = arglist.num_envs, arglist.max_episode_len
     if sp.name == "simple":
         raise AttributeError("'Scenario' object has no attribute 'benchmark_data' (scenario simple)")
+    if sp.name == "simple_speaker_listener":
+        raise NameError("simple_speaker_listener: upstream's benchmark_data names an undefined variable "
+                        "(it raises on its first call); --benchmark has nothing to record")
     open_eps = [[[]] for _ in range(E)]
     closed = []
     train_step = 0

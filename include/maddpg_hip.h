@@ -41,7 +41,7 @@ extern "C" {
 #endif
 
 #define MDP_MAX_AGENTS 8
-#define MDP_ACT_DIM 5          /* MPE Discrete(dim_p*2+1) action spaces */
+#define MDP_ACT_DIM 5          /* MPE Discrete(dim_p*2+1) action spaces; the widest (mdp_set_act_dims) */
 #define MDP_MAX_UNITS 256      /* largest --num-units (train.py:24) */
 /* Besides these bounds, a configuration must fit the kernels' LDS envelope (a
    16-row tile of every launch in a CU's 160 KB: the sum of obs dims up to
@@ -54,7 +54,8 @@ enum mdp_scenario {
     MDP_SCN_SIMPLE = 1,
     MDP_SCN_SPREAD = 2,
     MDP_SCN_ADVERSARY = 3,
-    MDP_SCN_TAG = 4
+    MDP_SCN_TAG = 4,
+    MDP_SCN_SPEAKER_LISTENER = 5  /* simple_speaker_listener: Discrete(3) speaker, Discrete(5) listener */
 };
 
 /* which parameter set of one agent (mdp_set_params / mdp_get_params) */
@@ -100,7 +101,7 @@ typedef struct mdp_config {
 
 typedef struct mdp_tensor_info {      /* one fully_connected{,_1,_2}/{weights,biases} */
     int64_t offset;                   /* floats from the start of a param-space region */
-    int32_t rows, cols;               /* the TF variable's shape ([in, num_units] ...) */
+    int32_t rows, cols;               /* the TF variable's shape ([in, num_units] ...; mdp_set_act_dims) */
     int32_t dev_rows, dev_cols;       /* its block in the arena: num_units padded to the
                                          kernel width (64/128/256), extra entries zero */
 } mdp_tensor_info;
@@ -125,6 +126,26 @@ int mdp_region(const mdp_handle* h, int32_t region, int64_t* offset, int64_t* by
 int mdp_tensor(const mdp_handle* h, int32_t agent, int32_t net, int32_t t, mdp_tensor_info* out);
 /* joint replay row layout: offsets (floats) of agent's obs/act/obs_next/rew/done, row stride */
 int mdp_row_layout(const mdp_handle* h, int32_t agent, int32_t out6[6]);
+/* Per-agent action widths: agent i has a Discrete(dims[i]) space, 1 <= dims[i] <=
+ * MDP_ACT_DIM (make_pdtype(act_space) per agent, maddpg.py:31,39; distributions.py:
+ * 413-415).  Default: MDP_ACT_DIM for every agent.  No device layout changes: the
+ * replay row's action slot, the critic-input columns, the actor's W3 / b3 block and
+ * every [.][MDP_ACT_DIM] action / noise array of this ABI stay MDP_ACT_DIM wide.
+ * Agent i uses the first dims[i] entries of its slot; the Gumbel-softmax runs over
+ * those only and writes exactly 0 to the pad entries, pad uniforms are never used,
+ * and pad parameters, targets, Adam slots and gradients stay exactly 0.  The
+ * logical shapes (mdp_tensor rows / cols, mdp_set_params / mdp_get_params) are the
+ * reference's: actor W3 [num_units, A_i], b3 [A_i]; critic W1 [sum_obs + sum_j A_j,
+ * num_units] (DDPG critic [obs_i + A_i, num_units]) -- the device block of that W1
+ * has interior pad rows, which are written as zero and never returned.  Rows given
+ * to mdp_buffer_add_rows / mdp_buffer_put_agent and actions given to mdp_env_step
+ * must hold zeros in the pad entries.
+ * Accepted only before the handle's first parameter write, act, update or env
+ * call; on a handle with a device scenario the widths must equal the scenario's
+ * own (such a handle needs no call).  < 0 with a message otherwise. */
+int mdp_set_act_dims(mdp_handle* h, const int32_t dims[MDP_MAX_AGENTS]);
+/* the widths in use (0 beyond n_agents) */
+int mdp_get_act_dims(const mdp_handle* h, int32_t dims[MDP_MAX_AGENTS]);
 
 /* ---- parameters (golden injection, checkpoint; tf_util.py:259-273) --- */
 int mdp_set_params(mdp_handle* h, int32_t agent, int32_t which, const float* src_host, int64_t n);
@@ -309,6 +330,16 @@ int mdp_env_step(mdp_handle* h, const float* act_in_dev, const float* u_dev);
 /* env state: pos/vel [E][n_entities][2] fp32, goal [E] int32, ep_step [E] int32 */
 int mdp_env_get_state(mdp_handle* h, float* pos_host, float* vel_host, int32_t* goal_host, int32_t* ep_step_host);
 int mdp_env_set_state(mdp_handle* h, const float* pos_host, const float* vel_host, const int32_t* goal_host, const int32_t* ep_step_host);
+/* Communication state (core.py agent.state.c) of every agent, [num_envs][n_agents][MDP_ACT_DIM]
+ * host floats; synchronises like mdp_env_get_state.  After a step a speaking agent's
+ * state.c is its action vector of that step (environment._set_action, no noise), a
+ * silent agent's is 0; everything is 0 after a reset.  Of the scenarios only
+ * simple_speaker_listener has a speaker (agent 0, Discrete(3); the listener's last 3
+ * observations are its state.c): on the others get returns zeros and set is refused.
+ * simple_speaker_listener is restated from memory of the upstream MPE source, which
+ * is neither vendored by the reference nor present here: its parity is UNPINNED. */
+int mdp_env_get_comm(mdp_handle* h, float* comm_host);
+int mdp_env_set_comm(mdp_handle* h, const float* comm_host);
 int mdp_env_obs(mdp_handle* h, float* obs_dev);   /* current obs [E][sum obs] */
 /* --benchmark mode (train.py:139-148): mdp_env_step that also writes every
  * agent's scenario benchmark_data() of the post-physics state (MPE

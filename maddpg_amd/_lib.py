@@ -19,12 +19,13 @@ LIB_PATH = os.environ.get("MDP_LIB") or os.path.join(HERE, "libmaddpg_hip.so")
 HEADER = os.path.join(os.path.dirname(HERE), "include", "maddpg_hip.h")
 
 MAX_AGENTS = 8
-ACT_DIM = 5
+ACT_DIM = 5   # MDP_ACT_DIM: the widest action space, and the width of every device action slot
 BENCH_W = 8   # MDP_BENCH_W: floats per agent benchmark_data record
 MAX_UNITS = 256  # MDP_MAX_UNITS: largest --num-units
 ABI_VERSION = 5
 
-SCN = {"none": 0, "simple": 1, "simple_spread": 2, "simple_adversary": 3, "simple_tag": 4}
+SCN = {"none": 0, "simple": 1, "simple_spread": 2, "simple_adversary": 3, "simple_tag": 4,
+       "simple_speaker_listener": 5}
 WHICH = {"actor": 0, "critic": 1, "tgt_actor": 2, "tgt_critic": 3, "m_actor": 4, "v_actor": 5,
          "m_critic": 6, "v_critic": 7, "g_actor": 8, "g_critic": 9}
 REGION = {"theta": 0, "target": 1, "adam_m": 2, "adam_v": 3, "grad": 4, "replay": 5, "index": 6,
@@ -89,6 +90,8 @@ SIGNATURES = {
     "mdp_region": (ctypes.c_int, [_P, _I32, ctypes.POINTER(_I64), ctypes.POINTER(_I64)]),
     "mdp_tensor": (ctypes.c_int, [_P, _I32, _I32, _I32, ctypes.POINTER(MdpTensorInfo)]),
     "mdp_row_layout": (ctypes.c_int, [_P, _I32, _I32P]),
+    "mdp_set_act_dims": (ctypes.c_int, [_P, _I32P]),
+    "mdp_get_act_dims": (ctypes.c_int, [_P, _I32P]),
     "mdp_set_params": (ctypes.c_int, [_P, _I32, _I32, _F32P, _I64]),
     "mdp_get_params": (ctypes.c_int, [_P, _I32, _I32, _F32P, _I64]),
     "mdp_get_beta_powers": (ctypes.c_int, [_P, _I32, _I32, _F32P]),
@@ -135,6 +138,8 @@ SIGNATURES = {
     "mdp_env_step": (ctypes.c_int, [_P, _P, _P]),
     "mdp_env_get_state": (ctypes.c_int, [_P, _F32P, _F32P, _I32P, _I32P]),
     "mdp_env_set_state": (ctypes.c_int, [_P, _F32P, _F32P, _I32P, _I32P]),
+    "mdp_env_get_comm": (ctypes.c_int, [_P, _F32P]),
+    "mdp_env_set_comm": (ctypes.c_int, [_P, _F32P]),
     "mdp_env_obs": (ctypes.c_int, [_P, _P]),
     "mdp_env_step_bench": (ctypes.c_int, [_P, _P]),
     "mdp_set_update_mode": (ctypes.c_int, [_P, _I32]),

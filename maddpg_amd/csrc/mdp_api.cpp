@@ -42,7 +42,10 @@ NDesc make_net(int64_t& off, int in, int H, int out) {
 }
 
 // scenario entity tables (multiagent/scenarios/*.py make_world)
-bool make_env(const mdp_config& c, EnvDesc& e, std::vector<int>& obs_dims, std::string& err) {
+// act_dims: the scenario's Discrete(k) widths (environment.py: dim_p * 2 + 1 = 5 for
+// a movable silent agent, dim_c for an immovable speaker)
+bool make_env(const mdp_config& c, EnvDesc& e, std::vector<int>& obs_dims, std::vector<int>& act_dims,
+              std::string& err) {
   std::memset(&e, 0, sizeof(e));
   e.scenario = c.scenario;
   e.max_ep_len = c.max_episode_len;
@@ -51,6 +54,7 @@ bool make_env(const mdp_config& c, EnvDesc& e, std::vector<int>& obs_dims, std::
   for (int i = 0; i < MDP_MAX_ENT; ++i) e.max_speed[i] = -1.f;
   for (int i = 0; i < MDP_MAX_AGENTS; ++i) e.accel[i] = 5.0f;
   obs_dims.assign(n, 0);
+  act_dims.assign(n, MDP_ACT_DIM);
   switch (c.scenario) {
     case MDP_SCN_SIMPLE:
       if (n != 1) { err = "simple has exactly 1 agent"; return false; }
@@ -104,6 +108,17 @@ bool make_env(const mdp_config& c, EnvDesc& e, std::vector<int>& obs_dims, std::
       }
       break;
     }
+    case MDP_SCN_SPEAKER_LISTENER:
+      // scenarios/simple_speaker_listener.py (restated from memory: parity UNPINNED)
+      if (n != 2) { err = "simple_speaker_listener has exactly 2 agents"; return false; }
+      e.n_landmarks = 3;
+      e.size[0] = e.size[1] = 0.075f;
+      e.movable[1] = 1;     // the listener; the speaker (agent 0) does not move and alone speaks (env_silent)
+      for (int l = 0; l < 3; ++l) e.size[n + l] = 0.04f;
+      obs_dims[0] = 3;                  // the goal landmark's colour
+      obs_dims[1] = 2 + 2 * 3 + 3;      // vel, 3 landmarks relative, the speaker's state.c
+      act_dims[0] = 3;                  // Discrete(dim_c)
+      break;
     default:
       err = "unknown scenario";
       return false;
@@ -158,6 +173,7 @@ bool build_layout(const mdp_config* c, Layout& L, std::string& err) {
     ADesc& a = T.ag[i];
     a.obs_dim = c->obs_dim[i];
     a.local_q = c->local_q[i] ? 1 : 0;
+    topo_set_act_w(T, i, MDP_ACT_DIM);  // mdp_set_act_dims narrows it; no layout depends on it
     a.obs_off = acc;
     a.act_off = sum_obs + MDP_ACT_DIM * i;
     a.nobs_off = sum_obs + MDP_ACT_DIM * n + acc;
@@ -170,6 +186,8 @@ bool build_layout(const mdp_config* c, Layout& L, std::string& err) {
     a.actor = make_net(off, a.obs_dim, H, MDP_ACT_DIM);
     a.critic = make_net(off, a.cin, H, 1);
   }
+  for (int w = 1; w <= MDP_ACT_DIM; ++w)
+    T.reg_scale_w[w - 1] = (float)(2.0 * (double)c->actor_reg / ((double)c->batch_size * w));
   T.cin_max = cin_max;
   L.PT = off;
   L.nwg = (c->batch_size + 15) / 16;
@@ -178,9 +196,10 @@ bool build_layout(const mdp_config* c, Layout& L, std::string& err) {
     L.slab_a = std::max(L.slab_a, T.ag[i].actor.size);
   }
   const int E = c->num_envs;
-  std::vector<int> dims;
+  std::vector<int> dims, widths;
   if (c->scenario != MDP_SCN_NONE) {
-    if (!make_env(*c, L.env, dims, err)) return false;
+    if (!make_env(*c, L.env, dims, widths, err)) return false;
+    for (int i = 0; i < n; ++i) topo_set_act_w(T, i, widths[i]);
     for (int i = 0; i < n; ++i)
       if (dims[i] != c->obs_dim[i]) {
         char b[160];
@@ -224,7 +243,9 @@ bool build_layout(const mdp_config* c, Layout& L, std::string& err) {
   sz[MDP_R_REPLAY] = 4 * c->capacity * T.row_stride;
   sz[MDP_R_INDEX] = 2 * 4 * (int64_t)n * c->batch_size;  // two slots: round r draws round r+1's
   sz[MDP_R_STATS] = 8 * 8 * (int64_t)n;
-  sz[MDP_R_ENV] = (int64_t)E * (4 * 4 * L.n_ent + 4 + 4 + 4 * n) + 64;
+  // (the comm state only where an agent speaks: the silent scenarios' layout is unchanged)
+  sz[MDP_R_ENV] = (int64_t)E * (4 * 4 * L.n_ent + 4 + 4 + 4 * n) + 64 +
+                  (env_dim_c(c->scenario) > 0 ? 4 * (int64_t)E * n * MDP_ACT_DIM : 0);
   sz[MDP_R_EPLOG] = 4 * (int64_t)L.eplog_rows * (1 + n);
   sz[MDP_R_BETA] = 4 * 8 * (int64_t)n;  // per optimizer: next powers (TF vars), powers of this step
   // per-agent blocks of partial gradients / stats / TD targets (throughput mode
@@ -290,6 +311,7 @@ struct mdp_handle {
   char* arena = nullptr;
   float *theta, *target, *m, *v, *grad, *replay, *beta, *slab_c, *slab_a, *eplog;
   float *pos, *vel, *ep_rew;
+  float* env_comm = nullptr;  // [E][n][MDP_ACT_DIM] state.c of every agent (scenarios with a speaker), else null
   int32_t *index, *goal, *ep_step;
   double *stats, *stat_c, *stat_a, *y;
   Ctl* ctl;
@@ -375,6 +397,7 @@ struct mdp_handle {
   // error| slots [n][B], one sum tree per agent
   bool per = false;
   bool trained = false;               // an update / train call was made (mdp_per_enable must precede it)
+  bool started = false;               // a parameter write, act, update or env call was made (mdp_set_act_dims must precede it)
   PerHdr* per_hdr = nullptr;
   PerState* per_st = nullptr;
   int32_t* per_idx = nullptr;
@@ -555,19 +578,49 @@ const NDesc& net_of(mdp_handle* h, int agent, int net) {
   return net ? h->L.topo.ag[agent].critic : h->L.topo.ag[agent].actor;
 }
 
-// logical (TF variable) shape of tensor t of a net whose device width is padded:
-// (W1 [in, u], b1 [u], W2 [u, u], b2 [u], W3 [u, out], b3 [out], u = --num-units)
-void logical_shape(const mdp_handle* h, const NDesc& d, int t, int* rows, int* cols) {
+// logical (TF variable) shape of tensor t of agent's net (0 actor, 1 critic),
+// whose device block is padded in the hidden width and in the action slots:
+// (W1 [in, u], b1 [u], W2 [u, u], b2 [u], W3 [u, out], b3 [out], u = --num-units;
+// the actor's out is the agent's action width A_i, the critic's in counts A_j
+// per action slot: sum_obs + sum_j A_j, or obs_i + A_i for a DDPG critic)
+void logical_shape(const mdp_handle* h, int agent, int net, int t, int* rows, int* cols) {
+  const Topo& T = h->L.topo;
+  const ADesc& ag = T.ag[agent];
+  const NDesc& d = net ? ag.critic : ag.actor;
   const int u = h->L.H_log;
   *rows = (t == 2 || t == 4) ? u : d.t[t].rows;
   *cols = t < 4 ? u : d.t[t].cols;
+  if (!net && t >= 4) *cols = topo_act_w(T, agent);
+  if (net && t == 0) {
+    int pad = MDP_ACT_DIM - topo_act_w(T, agent);
+    if (!ag.local_q) {
+      pad = 0;
+      for (int j = 0; j < T.n; ++j) pad += MDP_ACT_DIM - topo_act_w(T, j);
+    }
+    *rows = d.t[0].rows - pad;
+  }
 }
 
-int64_t net_floats(const mdp_handle* h, const NDesc& d) {
+// device row of logical row r of the critic's W1: the action slots are
+// MDP_ACT_DIM rows each on the device, A_j of them logical (interior padding)
+int critic_w1_dev_row(const mdp_handle* h, int agent, int r) {
+  const Topo& T = h->L.topo;
+  const ADesc& ag = T.ag[agent];
+  const int obs = ag.local_q ? ag.obs_dim : T.sum_obs;
+  if (r < obs || ag.local_q) return r;
+  int q = r - obs;
+  for (int j = 0; j < T.n; ++j) {
+    if (q < topo_act_w(T, j)) return obs + MDP_ACT_DIM * j + q;
+    q -= topo_act_w(T, j);
+  }
+  return -1;  // not reached: r is below the logical row count
+}
+
+int64_t net_floats(const mdp_handle* h, int agent, int net) {
   int64_t s = 0;
   for (int t = 0; t < 6; ++t) {
     int r, c;
-    logical_shape(h, d, t, &r, &c);
+    logical_shape(h, agent, net, t, &r, &c);
     s += (int64_t)r * c;
   }
   return s;
@@ -749,7 +802,7 @@ ApplyArgs apply_args(mdp_handle* h, int agent, int net, float scale, bool tp = f
   const double tau = (double)h->cfg.tau;
   a.pa = (float)(1.0 - tau);
   a.pb = (float)(1.0 - (1.0 - tau));
-  a.stats_mode = net ? 1 : 2;
+  a.stats_mode = net ? 1 : 1 + topo_act_w(h->L.topo, agent);
   a.slab_stat = net ? h->stat_c : h->stat_a;
   a.y = h->y;
   a.B = h->cfg.batch_size;
@@ -1507,7 +1560,9 @@ int mdp_create(const mdp_config* cfg, void* arena_dev, int64_t arena_bytes, void
     h->ep_step = (int32_t*)p;
     p += 4 * (int64_t)E;
     h->ep_rew = (float*)p;
-    (void)n;
+    p += 4 * (int64_t)E * n;
+    // behind the 64 spare bytes the region has always had: the older fields keep their places
+    if (env_dim_c(cfg->scenario) > 0) h->env_comm = (float*)(p + 64);
   }
   {
     char* p = (char*)R(MDP_R_SLAB);
@@ -1590,9 +1645,35 @@ int mdp_tensor(const mdp_handle* h, int32_t agent, int32_t net, int32_t t, mdp_t
   if (unusable(h) || agent < 0 || agent >= h->cfg.n_agents || t < 0 || t > 5 || !out) return -1;
   const NDesc& d = net ? h->L.topo.ag[agent].critic : h->L.topo.ag[agent].actor;
   out->offset = d.t[t].off;
-  logical_shape(h, d, t, &out->rows, &out->cols);
+  logical_shape(h, agent, net ? 1 : 0, t, &out->rows, &out->cols);
   out->dev_rows = d.t[t].rows;
   out->dev_cols = d.t[t].cols;
+  return 0;
+}
+
+// per-agent action widths (Discrete(A_i), A_i in 1..MDP_ACT_DIM).  No layout
+// depends on them (every slot stays MDP_ACT_DIM wide, pad entries zero), but
+// the zeros must be in place before anything is written or launched, and
+// captured graphs hold the widths: accepted only on a fresh handle.
+int mdp_set_act_dims(mdp_handle* h, const int32_t dims[MDP_MAX_AGENTS]) {
+  MDP_NEED(h);
+  if (!dims) return fail(h, "mdp_set_act_dims: dims is null");
+  if (h->started || h->trained)
+    return fail(h, "mdp_set_act_dims: call it before the handle's first parameter write, act, update or env call");
+  const int n = h->cfg.n_agents;
+  for (int i = 0; i < n; ++i)
+    if (dims[i] < 1 || dims[i] > MDP_ACT_DIM) return fail(h, "mdp_set_act_dims: every width must be in 1..5");
+  if (h->cfg.scenario != MDP_SCN_NONE)
+    for (int i = 0; i < n; ++i)
+      if (dims[i] != topo_act_w(h->L.topo, i))
+        return fail(h, "mdp_set_act_dims: widths differ from the scenario's own (a scenario handle needs no call)");
+  for (int i = 0; i < n; ++i) topo_set_act_w(h->L.topo, i, dims[i]);
+  return 0;
+}
+
+int mdp_get_act_dims(const mdp_handle* h, int32_t dims[MDP_MAX_AGENTS]) {
+  if (unusable(h) || !dims) return -1;
+  for (int i = 0; i < MDP_MAX_AGENTS; ++i) dims[i] = i < h->cfg.n_agents ? topo_act_w(h->L.topo, i) : 0;
   return 0;
 }
 
@@ -1613,14 +1694,17 @@ int mdp_set_params(mdp_handle* h, int32_t agent, int32_t which, const float* src
   int region, net;
   if (region_for(which, &region, &net)) return fail(h, "bad param set id");
   const NDesc& d = net_of(h, agent, net);
-  if (n != net_floats(h, d)) return fail(h, "param count mismatch");
+  if (n != net_floats(h, agent, net)) return fail(h, "param count mismatch");
+  h->started = true;
   std::vector<float> buf(d.size, 0.f);  // padded entries stay zero
   int64_t s = 0;
   for (int t = 0; t < 6; ++t) {
     int rows, cols;
-    logical_shape(h, d, t, &rows, &cols);
-    for (int r = 0; r < rows; ++r, s += cols)
-      std::memcpy(buf.data() + (d.t[t].off - d.off) + (int64_t)r * d.t[t].cols, src + s, 4 * (int64_t)cols);
+    logical_shape(h, agent, net, t, &rows, &cols);
+    for (int r = 0; r < rows; ++r, s += cols) {
+      const int dr = (net && t == 0) ? critic_w1_dev_row(h, agent, r) : r;
+      std::memcpy(buf.data() + (d.t[t].off - d.off) + (int64_t)dr * d.t[t].cols, src + s, 4 * (int64_t)cols);
+    }
   }
   float* dst = (float*)(h->arena + h->L.off[region]) + d.off;
   HIPCHK(h, hipMemcpyAsync(dst, buf.data(), 4 * buf.size(), hipMemcpyHostToDevice, h->stream));
@@ -1633,7 +1717,7 @@ int mdp_get_params(mdp_handle* h, int32_t agent, int32_t which, float* dst, int6
   int region, net;
   if (region_for(which, &region, &net)) return fail(h, "bad param set id");
   const NDesc& d = net_of(h, agent, net);
-  if (n != net_floats(h, d)) return fail(h, "param count mismatch");
+  if (n != net_floats(h, agent, net)) return fail(h, "param count mismatch");
   std::vector<float> buf(d.size);
   const float* src = (const float*)(h->arena + h->L.off[region]) + d.off;
   HIPCHK(h, hipMemcpyAsync(buf.data(), src, 4 * buf.size(), hipMemcpyDeviceToHost, h->stream));
@@ -1641,9 +1725,11 @@ int mdp_get_params(mdp_handle* h, int32_t agent, int32_t which, float* dst, int6
   int64_t s = 0;
   for (int t = 0; t < 6; ++t) {
     int rows, cols;
-    logical_shape(h, d, t, &rows, &cols);
-    for (int r = 0; r < rows; ++r, s += cols)
-      std::memcpy(dst + s, buf.data() + (d.t[t].off - d.off) + (int64_t)r * d.t[t].cols, 4 * (int64_t)cols);
+    logical_shape(h, agent, net, t, &rows, &cols);
+    for (int r = 0; r < rows; ++r, s += cols) {
+      const int dr = (net && t == 0) ? critic_w1_dev_row(h, agent, r) : r;
+      std::memcpy(dst + s, buf.data() + (d.t[t].off - d.off) + (int64_t)dr * d.t[t].cols, 4 * (int64_t)cols);
+    }
   }
   return 0;
 }
@@ -1776,6 +1862,7 @@ int mdp_act(mdp_handle* h, int32_t agent, int32_t target, const float* obs_dev, 
   if (bad_agent(h, agent)) return -1;
   if (rows <= 0) return 0;
   const ADesc& ag = h->L.topo.ag[agent];
+  h->started = true;
   MDP_DEV(h, obs_dev, 4 * (int64_t)rows * ag.obs_dim, "mdp_act", false);
   MDP_DEV(h, act_dev, 4 * (int64_t)rows * MDP_ACT_DIM, "mdp_act", false);
   MDP_DEV(h, u_dev, 4 * (int64_t)rows * MDP_ACT_DIM, "mdp_act", true);
@@ -1787,6 +1874,7 @@ int mdp_act(mdp_handle* h, int32_t agent, int32_t target, const float* obs_dev, 
   a.x = obs_dev;
   a.out = act_dev;
   a.gumbel = 1;
+  a.act_w = topo_act_w(h->L.topo, agent);
   a.u = u_dev;
   a.seed = h->cfg.seed;
   a.stream = 0x40000u | (uint32_t)(agent << 1) | (uint32_t)(target ? 1 : 0);
@@ -1800,6 +1888,7 @@ int mdp_actor_logits(mdp_handle* h, int32_t agent, int32_t target, const float* 
   if (bad_agent(h, agent)) return -1;
   if (rows <= 0) return 0;
   const ADesc& ag = h->L.topo.ag[agent];
+  h->started = true;
   MDP_DEV(h, obs_dev, 4 * (int64_t)rows * ag.obs_dim, "mdp_actor_logits", false);
   MDP_DEV(h, logits_dev, 4 * (int64_t)rows * MDP_ACT_DIM, "mdp_actor_logits", false);
   EvalArgs a;
@@ -1810,6 +1899,7 @@ int mdp_actor_logits(mdp_handle* h, int32_t agent, int32_t target, const float* 
   a.x = obs_dev;
   a.out = logits_dev;
   a.gumbel = 0;
+  a.act_w = MDP_ACT_DIM;
   a.u = nullptr;
   a.seed = h->cfg.seed;
   a.stream = 0;
@@ -1822,6 +1912,7 @@ int mdp_q_values(mdp_handle* h, int32_t agent, int32_t target, const float* x_de
   if (bad_agent(h, agent)) return -1;
   if (rows <= 0) return 0;
   const ADesc& ag = h->L.topo.ag[agent];
+  h->started = true;
   MDP_DEV(h, x_dev, 4 * (int64_t)rows * ag.cin, "mdp_q_values", false);
   MDP_DEV(h, q_dev, 4 * (int64_t)rows, "mdp_q_values", false);
   EvalArgs a;
@@ -1832,6 +1923,7 @@ int mdp_q_values(mdp_handle* h, int32_t agent, int32_t target, const float* x_de
   a.x = x_dev;
   a.out = q_dev;
   a.gumbel = 0;
+  a.act_w = MDP_ACT_DIM;
   a.u = nullptr;
   a.seed = h->cfg.seed;
   a.stream = 0;
@@ -2291,6 +2383,7 @@ int mdp_critic_grad(mdp_handle* h, int32_t agent, const int32_t* idx_dev, const 
 int mdp_actor_grad(mdp_handle* h, int32_t agent, const int32_t* idx_dev, const float* u_act_dev) {
   if (bad_agent(h, agent)) return -1;
   if (!idx_dev) return fail(h, "actor_grad needs indices");
+  h->started = true;
   MDP_DEV(h, idx_dev, 4 * (int64_t)h->cfg.batch_size, "mdp_actor_grad", false);
   MDP_DEV(h, u_act_dev, 4 * (int64_t)h->cfg.batch_size * MDP_ACT_DIM, "mdp_actor_grad", true);
   return do_actor_grad(h, agent, idx_dev, u_act_dev);
@@ -2319,6 +2412,7 @@ int mdp_get_stats(mdp_handle* h, int32_t agent, double out6[6]) {
 static int need_env(mdp_handle* h) {
   MDP_NEED(h);
   if (h->cfg.scenario == MDP_SCN_NONE || h->cfg.num_envs <= 0) return fail(h, "handle has no device env");
+  h->started = true;
   return 0;
 }
 
@@ -2335,6 +2429,7 @@ int mdp_env_reset(mdp_handle* h) {
   a.goal = h->goal;
   a.ep_step = h->ep_step;
   a.ep_rew = h->ep_rew;
+  a.comm = h->env_comm;
   HIPCHK(h, mdp_launch_env_reset(a, h->stream));
   h->env_lockstep = true;
   return 0;
@@ -2360,6 +2455,7 @@ static int env_step_launch(mdp_handle* h, const float* act_in_dev, const float* 
   a.goal = h->goal;
   a.ep_step = h->ep_step;
   a.ep_rew = h->ep_rew;
+  a.comm = h->env_comm;
   a.eplog = h->eplog;
   a.eplog_cap = h->L.eplog_rows;
   a.eplog_by_env = h->env_lockstep ? 1 : 0;
@@ -2402,6 +2498,9 @@ int mdp_env_step_bench(mdp_handle* h, float* info_dev) {
   MDP_DEV(h, info_dev, 4 * (int64_t)h->cfg.num_envs * h->cfg.n_agents * MDP_BENCH_W, "mdp_env_step_bench", false);
   if (h->cfg.scenario == MDP_SCN_SIMPLE)
     return fail(h, "scenario 'simple' has no benchmark_data (MPE Scenario attribute missing)");
+  if (h->cfg.scenario == MDP_SCN_SPEAKER_LISTENER)
+    return fail(h, "scenario 'simple_speaker_listener': upstream's benchmark_data raises (it names an undefined "
+                   "variable), so there is no record to return");
   const int rc = env_step_launch(h, nullptr, nullptr, info_dev);
   if (rc) return rc;
   advance_ring_mirror(h);
@@ -2603,6 +2702,30 @@ int mdp_env_set_state(mdp_handle* h, const float* pos, const float* vel, const i
   return 0;
 }
 
+// state.c of every agent, [E][n][MDP_ACT_DIM] host floats (zeros on a handle whose agents are all silent)
+int mdp_env_get_comm(mdp_handle* h, float* comm) {
+  if (need_env(h)) return -1;
+  if (!comm) return fail(h, "mdp_env_get_comm: comm is null");
+  const int64_t bytes = 4 * (int64_t)h->cfg.num_envs * h->cfg.n_agents * MDP_ACT_DIM;
+  if (!h->env_comm) {
+    std::memset(comm, 0, bytes);
+    return 0;
+  }
+  HIPCHK(h, hipMemcpyAsync(comm, h->env_comm, bytes, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  return 0;
+}
+
+int mdp_env_set_comm(mdp_handle* h, const float* comm) {
+  if (need_env(h)) return -1;
+  if (!comm) return fail(h, "mdp_env_set_comm: comm is null");
+  if (!h->env_comm) return fail(h, "mdp_env_set_comm: every agent of this scenario is silent (no comm state)");
+  const int64_t bytes = 4 * (int64_t)h->cfg.num_envs * h->cfg.n_agents * MDP_ACT_DIM;
+  HIPCHK(h, hipMemcpyAsync(h->env_comm, comm, bytes, hipMemcpyHostToDevice, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  return 0;
+}
+
 int mdp_env_obs(mdp_handle* h, float* obs_dev) {
   if (need_env(h)) return -1;
   {
@@ -2617,6 +2740,7 @@ int mdp_env_obs(mdp_handle* h, float* obs_dev) {
   a.pos = h->pos;
   a.vel = h->vel;
   a.goal = h->goal;
+  a.comm = h->env_comm;
   a.obs = obs_dev;
   HIPCHK(h, mdp_launch_env_obs(a, h->stream));
   return 0;

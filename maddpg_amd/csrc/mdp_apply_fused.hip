@@ -481,7 +481,7 @@ __device__ __forceinline__ void reduce_apply_body(const FusedApplyArgs& f, const
         a.stats_out[5] = sqrt(dv / a.B);
       }
     } else if (tid == 0) {
-      a.stats_out[1] = -s0 / a.B + (double)a.reg * (s1 / ((double)a.B * MDP_ACT_DIM));
+      a.stats_out[1] = -s0 / a.B + (double)a.reg * (s1 / ((double)a.B * (a.stats_mode - 1)));
     }
   }
   MDP_STAMP(33);

@@ -489,6 +489,39 @@ __device__ __forceinline__ void gumbel_softmax5(const float* logits, const float
   gumbel_noise5(u, gn);
   gumbel_softmax5_pre(logits, gn, a);
 }
+// An agent whose action space is Discrete(A), A < 5 (topo_act_w), keeps its
+// 5-wide slot everywhere; the sample is the softmax over the first A entries
+// and exactly 0.0f in the pad entries.  Pad logits and pad noise only pass
+// through selects (a NaN there changes nothing).  A == 5 runs the fixed-width
+// code above; A is the same in every lane of a wave at every call site but the
+// general critic step's, whose lanes cover several agents.
+__device__ __forceinline__ void gumbel_softmax_pre(const float* logits, const float* gn, float* a, int A) {
+  if (__builtin_expect(A == MDP_ACT_DIM, 1)) {  // (the narrow form laid out behind the hot code)
+    gumbel_softmax5_pre(logits, gn, a);
+    return;
+  }
+  float z[MDP_ACT_DIM];
+  float m = -INFINITY;
+#pragma unroll
+  for (int k = 0; k < MDP_ACT_DIM; ++k) {
+    z[k] = logits[k] - gn[k];
+    m = k < A ? fmaxf(m, z[k]) : m;
+  }
+  float s = 0.f;
+#pragma unroll
+  for (int k = 0; k < MDP_ACT_DIM; ++k) {
+    z[k] = k < A ? __expf(z[k] - m) : 0.f;
+    s += z[k];
+  }
+  const float inv = __builtin_amdgcn_rcpf(s);
+#pragma unroll
+  for (int k = 0; k < MDP_ACT_DIM; ++k) a[k] = z[k] * inv;
+}
+__device__ __forceinline__ void gumbel_softmax(const float* logits, const float* u, float* a, int A) {
+  float gn[MDP_ACT_DIM];
+  gumbel_noise5(u, gn);
+  gumbel_softmax_pre(logits, gn, a, A);
+}
 
 // ------------------------------------------------------ phase-parallel tiles
 // (k_critic_grad / k_actor_grad, 512-thread workgroups)  A "job" is one dense

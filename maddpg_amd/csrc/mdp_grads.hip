@@ -548,7 +548,7 @@ __device__ __forceinline__ void critic_body(const A& a, const Topo& T, const int
       } else {
         uniforms5(a.seed, (uint32_t)((a.agent << 8) | (j + 1)), ctr, (uint32_t)(r0 + row), u);
       }
-      gumbel_softmax5(lg + jb * MDP_R * 8 + row * 8, u, act);
+      gumbel_softmax(lg + jb * MDP_R * 8 + row * 8, u, act, topo_act_w(T, j));
       const int dst = lq ? ag.obs_dim : T.sum_obs + MDP_ACT_DIM * j;
       for (int k = 0; k < MDP_ACT_DIM; ++k) xt[row * ldc + dst + k] = act[k];
     }
@@ -767,7 +767,7 @@ __device__ __forceinline__ void actor_body(const AA& a, const Topo& T, const int
       } else {
         uniforms5(a.seed, (uint32_t)((a.agent << 8) | 0x80), ctr, (uint32_t)(r0 + lane), u);
       }
-      gumbel_softmax5(lg + lane * 8, u, av + lane * 8);
+      gumbel_softmax(lg + lane * 8, u, av + lane * 8, topo_act_w(T, a.agent));
       if (!par)
         for (int k = 0; k < MDP_ACT_DIM; ++k) x[lane * ldc + ag.a_in_off + k] = av[lane * 8 + k];
     }
@@ -852,10 +852,12 @@ __device__ __forceinline__ void actor_body(const AA& a, const Topo& T, const int
     // softmax backward + regulariser: dlogits = (da - sum(a*da)) * a + reg*2*p/(B*A); loss partials
     double s_q = 0.0, s_p = 0.0;
     if (lane < MDP_R) {
+      const int aw = topo_act_w(T, a.agent);
+      const float reg_scale = __builtin_expect(aw == MDP_ACT_DIM, 1) ? a.reg_scale : T.reg_scale_w[aw - 1];
       float dot = 0.f;
       for (int k = 0; k < MDP_ACT_DIM; ++k) dot += da[lane * 8 + k] * av[lane * 8 + k];
       for (int k = 0; k < MDP_ACT_DIM; ++k) {
-        const float g = (da[lane * 8 + k] - dot) * av[lane * 8 + k] + lg[lane * 8 + k] * a.reg_scale;
+        const float g = (da[lane * 8 + k] - dot) * av[lane * 8 + k] + lg[lane * 8 + k] * reg_scale;
         dl[lane * 8 + k] = lane < nvalid ? g : 0.f;
       }
       if (lane < nvalid) {

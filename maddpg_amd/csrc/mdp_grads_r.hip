@@ -269,7 +269,7 @@ __device__ __forceinline__ void dw3a_store(const float* gwpart, const float* dl,
 __device__ __forceinline__ void actor_fwd_wave(const float* __restrict__ P, const NDesc& na, const ADesc& ag,
                                                const float* rowbuf, int ldr, const float* u_act, int nvalid, int r0,
                                                uint64_t seed, int agent, uint32_t ctr, int* rows_ready, int nsig,
-                                               float* h1a, float* h2a, float* lg, float* av) {
+                                               float* h1a, float* h2a, float* lg, float* av, int act_w) {
   const int lane = threadIdx.x & 63, r = lane & 15, kq = lane >> 4;
   f32x4 w1[16], w2[16];
   float w3[16];
@@ -312,7 +312,7 @@ __device__ __forceinline__ void actor_fwd_wave(const float* __restrict__ P, cons
     }
   }
   wave_sync();
-  if (lane < MDP_R) gumbel_softmax5_pre(lg + lane * 8, gn, av + lane * 8);
+  if (lane < MDP_R) gumbel_softmax_pre(lg + lane * 8, gn, av + lane * 8, act_w);
 }
 
 // float4 q of a row block [16][MDP_APRE_W] <-> its LDS home (h1a | h2a | lg | av)
@@ -324,6 +324,15 @@ __device__ __forceinline__ float* apre_lds(int q, float* h1a, float* h2a, float*
 
 // extra workgroup of k_critic_grad_r: the actor forward + sample of row tile bx
 // for the actor step that follows (same agent, same indices, same noise)
+// NARROW (k_critic_grad_r, k_actor_grad_r and their extra-workgroup roles): the
+// instantiation launched when some agent's action width is below 5.  The other
+// one takes every width as the constant 5 and is, instruction for instruction,
+// the kernel of before (the widths in the Topo are not read).
+template <bool NARROW>
+__device__ __forceinline__ int act_w_of(const Topo& T, int j) {
+  return NARROW ? topo_act_w(T, j) : MDP_ACT_DIM;
+}
+template <bool NARROW>
 __device__ __forceinline__ void actor_pre_tile(const CriticArgs& a, float* lds, int* rows_ready, int bx) {
   const Topo& T = a.topo;
   const ADesc& ag = T.ag[a.agent];
@@ -340,7 +349,7 @@ __device__ __forceinline__ void actor_pre_tile(const CriticArgs& a, float* lds, 
   __syncthreads();
   if (wave == 0) {
     actor_fwd_wave(a.theta, ag.actor, ag, rowbuf, ldr, a.u_act, nvalid, r0, a.seed, a.agent, ctr_load(a.ctl),
-                   rows_ready, 7, h1a, h2a, lg, av);
+                   rows_ready, 7, h1a, h2a, lg, av, act_w_of<NARROW>(T, a.agent));
   } else {
     gather_rows16_part(a.replay, T.row_stride, a.idx, r0, nvalid, rowbuf, ldr, 64, 448);
     lds_signal(rows_ready);
@@ -371,6 +380,7 @@ __device__ __forceinline__ int cpre_split(int p) { return (MDP_ACT_DIM * p) / 4;
 // accumulator over obs' and a~_j, j != p (:104; p's weight rows read as zero)
 // -- into cpre.  Roles as k_critic_grad_r: waves 0..2 target actors, wave 3
 // the critic, waves 4..7 gather and one target-critic column tile each.
+template <bool NARROW>
 __device__ __forceinline__ void critic_pre_tile(const ActorArgs& a, float* lds, int* rows_ready, int bx) {
   const Topo& T = a.topo;
   const int k = a.cpre_agent, p = a.agent;
@@ -448,7 +458,7 @@ __device__ __forceinline__ void critic_pre_tile(const ActorArgs& a, float* lds, 
       wave_sync();
       if (lane < MDP_R) {
         float act[MDP_ACT_DIM];
-        gumbel_softmax5_pre(lgj + lane * 8, gn, act);
+        gumbel_softmax_pre(lgj + lane * 8, gn, act, act_w_of<NARROW>(T, j));
         for (int q = 0; q < MDP_ACT_DIM; ++q) xa[lane * ldA + MDP_ACT_DIM * j + q] = act[q];
       }
     } else if (wave == p && lane < MDP_R) {  // p's slot: zero weights meet zeros (not stale LDS, e.g. NaN)
@@ -530,9 +540,10 @@ __device__ __forceinline__ void critic_pre_tile(const ActorArgs& a, float* lds, 
 
 // PER: the prioritized-replay twin (A = CriticArgsPer: a.is_w / a.td_out); the
 // uniform kernel (A = CriticArgs) carries none of its code or arguments
-template <bool PER, class A>
+template <bool PER, bool NARROW, class A>
 __global__ __launch_bounds__(512) void k_critic_grad_r(A a) {
   MDP_KARG_TOUCH("s"(a.agent), "s"(a.inv_b), "s"(a.pf_count), "s"(a.cpre_prev), "s"(a.topo.n), "s"(gridDim.x));
+  if constexpr (NARROW) MDP_KARG_TOUCH("s"(a.topo.act_w4));
   BUD_BEGIN(0, a.agent, a.multi);
   MDP_WG_START(0);
   MDP_TL(a.ctl, 0, 0);
@@ -553,7 +564,7 @@ __global__ __launch_bounds__(512) void k_critic_grad_r(A a) {
     const int nwg = (a.B + MDP_RW - 1) / MDP_RW;
     if (bx >= nwg) {
       MDP_TL_ROLE(0, 1);
-      actor_pre_tile(a, lds, &rows_ready, bx - nwg);
+      actor_pre_tile<NARROW>(a, lds, &rows_ready, bx - nwg);
       MDP_WG_END(0);
       return;
     }
@@ -703,7 +714,7 @@ __global__ __launch_bounds__(512) void k_critic_grad_r(A a) {
         wave_sync();
         if (lane < MDP_R) {  // distributions.py:264-266
           float act[MDP_ACT_DIM];
-          gumbel_softmax5_pre(lgj + lane * 8, gn, act);
+          gumbel_softmax_pre(lgj + lane * 8, gn, act, act_w_of<NARROW>(T, pprev));
           for (int c = 0; c < MDP_ACT_DIM; ++c) xa[lane * ldA + MDP_ACT_DIM * pprev + c] = act[c];
         }
         MDP_STAMPW(52);
@@ -787,7 +798,7 @@ __global__ __launch_bounds__(512) void k_critic_grad_r(A a) {
       if (lane < MDP_R) {  // distributions.py:264-266
         const int row = lane;
         float act[MDP_ACT_DIM];
-        gumbel_softmax5_pre(lgj + row * 8, gn, act);
+        gumbel_softmax_pre(lgj + row * 8, gn, act, act_w_of<NARROW>(T, j));
         const int dst = lq ? 0 : MDP_ACT_DIM * j;
         for (int k = 0; k < MDP_ACT_DIM; ++k) xa[row * ldA + dst + k] = act[k];
       }
@@ -998,8 +1009,10 @@ __global__ __launch_bounds__(512) void k_critic_grad_r(A a) {
 }
 
 
+template <bool NARROW>
 __global__ __launch_bounds__(512) void k_actor_grad_r(ActorArgs a) {
   MDP_KARG_TOUCH("s"(a.agent), "s"(a.slab_stride), "s"(a.cpre_agent), "s"(a.topo.n), "s"(gridDim.x));
+  if constexpr (NARROW) MDP_KARG_TOUCH("s"(a.topo.act_w4));
   extern __shared__ __attribute__((aligned(16))) float lds[];
   __shared__ int rows_ready;
   __shared__ int fwd_issued;  // waves 0..3 issued the loads the critic forward needs first
@@ -1011,7 +1024,7 @@ __global__ __launch_bounds__(512) void k_actor_grad_r(ActorArgs a) {
     const int nwg = (a.B + MDP_RW - 1) / MDP_RW;
     if (bx >= nwg) {
       MDP_TL_ROLE(2, 1);
-      critic_pre_tile(a, lds, &rows_ready, bx - nwg);
+      critic_pre_tile<NARROW>(a, lds, &rows_ready, bx - nwg);
       MDP_WG_END(1);
       return;
     }
@@ -1096,7 +1109,7 @@ __global__ __launch_bounds__(512) void k_actor_grad_r(ActorArgs a) {
       } else {
         lds_signal(&fwd_issued);
         actor_fwd_wave(P, na, ag, rowbuf, ldr, u_act, nvalid, r0, a.seed, agent, ctr, &rows_ready, 6, h1a, h2a, lg,
-                       av);
+                       av, act_w_of<NARROW>(T, agent));
         // backward-phase weights: W1c rows of the a_i input (for da) and W3 of the actor (for d2a)
         rdg_load(wda, P + nc.t[0].off + ag.a_in_off * RH, min(r, MDP_ACT_DIM - 1), r < MDP_ACT_DIM);
 #pragma unroll
@@ -1125,10 +1138,12 @@ __global__ __launch_bounds__(512) void k_actor_grad_r(ActorArgs a) {
       wave_sync();
       // softmax backward + regulariser: dlogits = (da - sum(a da)) a + reg 2 p / (B A); loss terms
       if (lane < MDP_R) {
+        const int aw = act_w_of<NARROW>(T, agent);
+        const float reg_scale = aw == MDP_ACT_DIM ? a.reg_scale : T.reg_scale_w[aw - 1];
         float dot = 0.f;
         for (int k = 0; k < MDP_ACT_DIM; ++k) dot += da[lane * 8 + k] * av[lane * 8 + k];
         for (int k = 0; k < MDP_ACT_DIM; ++k) {
-          const float g = (da[lane * 8 + k] - dot) * av[lane * 8 + k] + lg[lane * 8 + k] * a.reg_scale;
+          const float g = (da[lane * 8 + k] - dot) * av[lane * 8 + k] + lg[lane * 8 + k] * reg_scale;
           dl[lane * 8 + k] = lane < nvalid ? g : 0.f;
         }
         if (lane < nvalid) {
@@ -1261,23 +1276,34 @@ hipError_t launch_r(K kern, const A& a, int lds, hipStream_t s, bool& attr, int 
 }
 }  // namespace
 
+// some agent of the topology narrower than MDP_ACT_DIM: the NARROW instantiations
+static bool topo_narrow(const Topo& t) {
+  for (int j = 0; j < t.n; ++j)
+    if (topo_act_w(t, j) != MDP_ACT_DIM) return true;
+  return false;
+}
+
 hipError_t mdp_launch_critic_grad_r(const CriticArgs& a, int lds_bytes, hipStream_t s) {
-  static bool attr = false;
+  static bool attr = false, attr_n = false;
   const int per = (a.B + MDP_RW - 1) / MDP_RW;
   // grid: critic row tiles | actor-forward row tiles (a.apre) | the index draw (pf_count; last)
-  return launch_r(k_critic_grad_r<false, CriticArgs>, a, lds_bytes, s, attr,
-                  (a.apre ? per : 0) + (a.pf_count > 0 ? 1 : 0));
+  const int extra = (a.apre ? per : 0) + (a.pf_count > 0 ? 1 : 0);
+  if (topo_narrow(a.topo)) return launch_r(k_critic_grad_r<false, true, CriticArgs>, a, lds_bytes, s, attr_n, extra);
+  return launch_r(k_critic_grad_r<false, false, CriticArgs>, a, lds_bytes, s, attr, extra);
 }
 hipError_t mdp_launch_critic_grad_r_per(const CriticArgsPer& a, int lds_bytes, hipStream_t s) {
-  static bool attr = false;
+  static bool attr = false, attr_n = false;
   const int per = (a.B + MDP_RW - 1) / MDP_RW;
-  return launch_r(k_critic_grad_r<true, CriticArgsPer>, a, lds_bytes, s, attr,
-                  (a.apre ? per : 0) + (a.pf_count > 0 ? 1 : 0));
+  const int extra = (a.apre ? per : 0) + (a.pf_count > 0 ? 1 : 0);
+  if (topo_narrow(a.topo)) return launch_r(k_critic_grad_r<true, true, CriticArgsPer>, a, lds_bytes, s, attr_n, extra);
+  return launch_r(k_critic_grad_r<true, false, CriticArgsPer>, a, lds_bytes, s, attr, extra);
 }
 hipError_t mdp_launch_actor_grad_r(const ActorArgs& a, int lds_bytes, hipStream_t s) {
-  static bool attr = false;
+  static bool attr = false, attr_n = false;
   // grid: actor row tiles | the next critic step's row tiles (a.cpre)
-  return launch_r(k_actor_grad_r, a, lds_bytes, s, attr, a.cpre ? (a.B + MDP_RW - 1) / MDP_RW : 0);
+  const int extra = a.cpre ? (a.B + MDP_RW - 1) / MDP_RW : 0;
+  if (topo_narrow(a.topo)) return launch_r(k_actor_grad_r<true>, a, lds_bytes, s, attr_n, extra);
+  return launch_r(k_actor_grad_r<false>, a, lds_bytes, s, attr, extra);
 }
 
 #ifdef MDP_TIMELINE

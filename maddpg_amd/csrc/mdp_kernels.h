@@ -87,7 +87,7 @@ struct ActorArgsHead {
   uint64_t seed;
   const Ctl* ctl;
   float neg_inv_b;      // dL/dq = -1/B
-  float reg_scale;      // 2 * actor_reg / (B * 5)
+  float reg_scale;      // 2 * actor_reg / (B * 5) (an agent narrower than 5: Topo::reg_scale_w)
   float* slab;
   int slab_stride;
   double* slab_stat;
@@ -141,7 +141,9 @@ struct ApplyArgs {
   float* beta;          // [2] beta1^t, beta2^t of this optimizer
   int polyak;
   float pa, pb;         // fp32(1 - tau), fp32(1 - (1 - tau))
-  int stats_mode;       // 0 none, 1 critic, 2 actor
+  // 0 none, 1 critic, 1 + A actor (A = the agent's action width, 6 for Discrete(5):
+  // the p_reg stat is the mean of its B * A squared logits)
+  int stats_mode;
   const double* slab_stat;
   const double* y;
   int B;
@@ -297,6 +299,7 @@ struct RolloutArgs {
   // consecutive env steps in this launch (1; > 1 only with one env workgroup,
   // no draw, no bench records and the policies' own actions)
   int nsteps;
+  float* comm;  // [E][n][MDP_ACT_DIM] agents' state.c, or null (every agent silent: env_dim_c == 0)
 };
 
 struct EnvResetArgs {
@@ -309,6 +312,7 @@ struct EnvResetArgs {
   int32_t* goal;
   int32_t* ep_step;
   float* ep_rew;
+  float* comm;  // as RolloutArgs::comm
 };
 
 struct EnvObsArgs {
@@ -318,6 +322,7 @@ struct EnvObsArgs {
   const float* pos;
   const float* vel;
   const int32_t* goal;
+  const float* comm;  // as RolloutArgs::comm
   float* obs;
 };
 
@@ -331,6 +336,7 @@ struct EvalArgs {
   const float* u;
   uint64_t seed;
   uint32_t stream, ctr;
+  int act_w;  // gumbel: the agent's action width (topo_act_w)
 };
 
 // kernel width that serves --num-units u: the gradient / rollout / eval kernels

@@ -382,7 +382,7 @@ __global__ __launch_bounds__(256) void k_apply(ApplyArgs a) {
           a.stats_out[5] = sqrt(dv / a.B);
         }
       } else if (tid == 0) {
-        a.stats_out[1] = -s0 / a.B + (double)a.reg * (s1 / ((double)a.B * MDP_ACT_DIM));
+        a.stats_out[1] = -s0 / a.B + (double)a.reg * (s1 / ((double)a.B * (a.stats_mode - 1)));
       }
     }
   }
@@ -476,6 +476,27 @@ __device__ inline void env_obs(const EnvDesc& E, const float* p, const float* v,
   }
 }
 
+// the same for a scenario with a speaking agent (env_dim_c > 0; kept apart
+// from env_obs so the silent scenarios' code is what it was).  comm: this env's
+// [n][MDP_ACT_DIM] communication state, or null for all zero
+__device__ inline void env_obs_comm(const EnvDesc& E, const float* p, const float* v, int goal, int i, float* o,
+                                    const float* comm) {
+  const int n = E.n_agents, L = E.n_landmarks;
+  int c = 0;
+  if (E.scenario != MDP_SCN_SPEAKER_LISTENER) return;
+  if (i == 0) {  // speaker: the goal landmark's colour
+    for (int l = 0; l < L; ++l) o[c++] = l == goal ? 0.65f : 0.15f;
+  } else {       // listener: velocity, landmarks relative to it, the speaker's state.c
+    o[c++] = v[2 * i];
+    o[c++] = v[2 * i + 1];
+    for (int l = 0; l < L; ++l) {
+      o[c++] = p[2 * (n + l)] - p[2 * i];
+      o[c++] = p[2 * (n + l) + 1] - p[2 * i + 1];
+    }
+    for (int k = 0; k < env_dim_c(E.scenario); ++k) o[c++] = comm ? comm[k] : 0.f;
+  }
+}
+
 // rewards of all agents (scenario reward() + shared reward for collaborative worlds)
 __device__ inline void env_reward(const EnvDesc& E, const float* p, int goal, float* rew) {
   const int n = E.n_agents, L = E.n_landmarks;
@@ -483,6 +504,13 @@ __device__ inline void env_reward(const EnvDesc& E, const float* p, int goal, fl
     case MDP_SCN_SIMPLE: {
       const float dx = p[0] - p[2 * n], dy = p[1] - p[2 * n + 1];
       rew[0] = -(dx * dx + dy * dy);
+      break;
+    }
+    case MDP_SCN_SPEAKER_LISTENER: {  // -|listener - goal|^2 for each; collaborative: both get the sum
+      const int g = n + goal;
+      const float dx = p[2] - p[2 * g], dy = p[3] - p[2 * g + 1];
+      const float r = -(dx * dx + dy * dy);
+      rew[0] = rew[1] = r + r;
       break;
     }
     case MDP_SCN_SPREAD: {
@@ -720,7 +748,7 @@ __device__ inline void env_reset_one(const EnvDesc& E, uint64_t seed, uint32_t s
     v[2 * e] = 0.f;
     v[2 * e + 1] = 0.f;
   }
-  if (E.scenario == MDP_SCN_ADVERSARY) {
+  if (E.scenario == MDP_SCN_ADVERSARY || E.scenario == MDP_SCN_SPEAKER_LISTENER) {
     int g = (int)(next_u() * E.n_landmarks);
     *goal = g < E.n_landmarks ? g : E.n_landmarks - 1;
   } else {
@@ -744,6 +772,8 @@ __global__ __launch_bounds__(256) void k_env_reset(EnvResetArgs a) {
   a.goal[e] = g;
   a.ep_step[e] = 0;
   for (int j = 0; j < a.env.n_agents; ++j) a.ep_rew[(int64_t)e * a.env.n_agents + j] = 0.f;
+  if (a.comm)
+    for (int q = 0; q < a.env.n_agents * MDP_ACT_DIM; ++q) a.comm[(int64_t)e * a.env.n_agents * MDP_ACT_DIM + q] = 0.f;
 }
 
 // current observations [E][sum_obs]
@@ -754,7 +784,10 @@ __global__ __launch_bounds__(256) void k_env_obs(EnvObsArgs a) {
   const float* p = a.pos + (int64_t)e * 2 * ne;
   const float* v = a.vel + (int64_t)e * 2 * ne;
   float* o = a.obs + (int64_t)e * a.topo.sum_obs;
-  for (int j = 0; j < a.env.n_agents; ++j) env_obs(a.env, p, v, a.goal[e], j, o + a.topo.ag[j].obs_off);
+  for (int j = 0; j < a.env.n_agents; ++j) {
+    if (a.comm) env_obs_comm(a.env, p, v, a.goal[e], j, o + a.topo.ag[j].obs_off, a.comm + (int64_t)e * a.env.n_agents * MDP_ACT_DIM);
+    else env_obs(a.env, p, v, a.goal[e], j, o + a.topo.ag[j].obs_off);
+  }
 }
 
 // One vector env step for 16 env copies per workgroup (train.py:112-128).
@@ -878,7 +911,13 @@ __global__ __launch_bounds__(MDP_NT) void k_rollout(RolloutArgs a) {
   static_assert(MDP_R * MDP_MAX_AGENTS <= MDP_NT, "rollout obs: one pass");
   if (tid < MDP_R * n) {
     const int r = tid / n, j = tid - r * n;
-    env_obs(E, sp + r * 2 * MDP_MAX_ENT, sv + r * 2 * MDP_MAX_ENT, sgoal[r], j, rowt + r * ldr + T.ag[j].obs_off);
+    // (state.c of the previous step: written by this workgroup's own threads in a
+    // multi-step launch, visible after the barriers in between)
+    if (__builtin_expect(a.comm != nullptr, 0))
+      env_obs_comm(E, sp + r * 2 * MDP_MAX_ENT, sv + r * 2 * MDP_MAX_ENT, sgoal[r], j, rowt + r * ldr + T.ag[j].obs_off,
+                   r < nvalid ? a.comm + (int64_t)(e0 + r) * n * MDP_ACT_DIM : nullptr);
+    else
+      env_obs(E, sp + r * 2 * MDP_MAX_ENT, sv + r * 2 * MDP_MAX_ENT, sgoal[r], j, rowt + r * ldr + T.ag[j].obs_off);
   }
   __syncthreads();
 
@@ -942,7 +981,7 @@ __global__ __launch_bounds__(MDP_NT) void k_rollout(RolloutArgs a) {
           }
         }
         wave_sync();
-        if (lane < MDP_R) gumbel_softmax5(lgj + lane * 8, u, rowt + lane * ldr + aj.act_off);
+        if (lane < MDP_R) gumbel_softmax(lgj + lane * 8, u, rowt + lane * ldr + aj.act_off, topo_act_w(T, j));
       }
       __syncthreads();
       MDP_STAMP(42);
@@ -975,7 +1014,7 @@ __global__ __launch_bounds__(MDP_NT) void k_rollout(RolloutArgs a) {
         } else {
           uniforms5(a.seed, 0x10000u | (uint32_t)j, step_s(), (uint32_t)(a.env_base + e0 + tid), u);
         }
-        gumbel_softmax5(lg + tid * 8, u, dst);
+        gumbel_softmax(lg + tid * 8, u, dst, topo_act_w(T, j));
       }
     }
     __syncthreads();
@@ -1024,9 +1063,21 @@ __global__ __launch_bounds__(MDP_NT) void k_rollout(RolloutArgs a) {
       a.ep_step[e] = st;
       if (MULTI) ep_st = st;
     }
+    if (__builtin_expect(a.comm != nullptr, 0)) {  // World.step: state.c = action.c of a speaking agent, 0 of a silent one; 0 after reset_world
+      float* cm = a.comm + (int64_t)e * n * MDP_ACT_DIM;
+      for (int j = 0; j < n; ++j)
+        for (int k = 0; k < MDP_ACT_DIM; ++k)
+          cm[j * MDP_ACT_DIM + k] = (term || env_silent(E.scenario, j)) ? 0.f : row[T.ag[j].act_off + k];
+    }
   } else if (tid >= 64 && tid - 64 < nvalid * n) {
     const int q = tid - 64, r = q / n, j = q - r * n;
-    env_obs(E, sp + r * 2 * MDP_MAX_ENT, sv + r * 2 * MDP_MAX_ENT, sgoal[r], j, rowt + r * ldr + T.ag[j].nobs_off);
+    // state.c after the step is the speaker's action vector of this step: the
+    // row's action block [n][MDP_ACT_DIM] (only a speaking agent's slot is read)
+    if (__builtin_expect(a.comm != nullptr, 0))
+      env_obs_comm(E, sp + r * 2 * MDP_MAX_ENT, sv + r * 2 * MDP_MAX_ENT, sgoal[r], j, rowt + r * ldr + T.ag[j].nobs_off,
+                   rowt + r * ldr + T.ag[0].act_off);
+    else
+      env_obs(E, sp + r * 2 * MDP_MAX_ENT, sv + r * 2 * MDP_MAX_ENT, sgoal[r], j, rowt + r * ldr + T.ag[j].nobs_off);
   }
   static_assert(64 + MDP_R * MDP_MAX_AGENTS <= MDP_NT, "rollout obs': one pass on waves 1..");
   __syncthreads();
@@ -1091,7 +1142,7 @@ __global__ __launch_bounds__(MDP_NT) void k_mlp_eval(EvalArgs a) {
       } else {
         uniforms5(a.seed, a.stream, a.ctr, (uint32_t)row, u);
       }
-      gumbel_softmax5(lg + tid * 8, u, act);
+      gumbel_softmax(lg + tid * 8, u, act, a.act_w);
       for (int k = 0; k < MDP_ACT_DIM; ++k) a.out[(int64_t)row * MDP_ACT_DIM + k] = act[k];
     } else {
       for (int k = 0; k < a.net.out; ++k) a.out[(int64_t)row * a.net.out + k] = lg[tid * 8 + k];

@@ -34,7 +34,23 @@ struct ADesc {
 struct Topo {
   int n, H, row_stride, sum_obs, cin_max, obs_max;
   ADesc ag[MDP_MAX_AGENTS];
+  // Per-agent action widths: agent j has a Discrete(A_j) space, A_j in
+  // 1..MDP_ACT_DIM (mdp_set_act_dims), 4 bits each (topo_act_w).  Every layout
+  // keeps the agent's slot MDP_ACT_DIM wide: the replay row, the critic input
+  // columns, the actor's W3 / b3.  The agent uses the first A_j entries; the
+  // pad entries are exactly zero everywhere.  (Behind the descriptors, in one
+  // word: the argument blocks of the gradient kernels end with their Topo, so
+  // every field the all-5 path reads stays where it was.)
+  uint32_t act_w4;
+  float reg_scale_w[MDP_ACT_DIM];  // actor regulariser 2 * actor_reg / (B * A) for A = 1..5 (A < 5: ActorArgs::reg_scale is A = 5's)
 };
+#if defined(__HIPCC__)
+__host__ __device__
+#endif
+inline int topo_act_w(const Topo& t, int j) { return (int)((t.act_w4 >> (4 * j)) & 7u); }
+inline void topo_set_act_w(Topo& t, int j, int w) {
+  t.act_w4 = (t.act_w4 & ~(7u << (4 * j))) | ((uint32_t)w << (4 * j));
+}
 
 // MPE entity table for the device env (multiagent/core.py Entity/Agent fields)
 struct EnvDesc {
@@ -46,6 +62,18 @@ struct EnvDesc {
   int movable[MDP_MAX_ENT];
   int adversary[MDP_MAX_AGENTS];
 };
+// communication (core.py world.dim_c, agent.silent): 0 when every agent of the
+// scenario is silent (no comm state in the arena); a speaking agent's state.c
+// is its action vector of the step (environment._set_action, no c noise).
+// Only simple_speaker_listener speaks: dim_c 3, agent 0 the speaker.
+#if defined(__HIPCC__)
+__host__ __device__
+#endif
+inline int env_dim_c(int scenario) { return scenario == MDP_SCN_SPEAKER_LISTENER ? 3 : 0; }
+#if defined(__HIPCC__)
+__host__ __device__
+#endif
+inline bool env_silent(int scenario, int agent) { return !(scenario == MDP_SCN_SPEAKER_LISTENER && agent == 0); }
 
 // device control block (one per handle, in the arena)
 struct Ctl {

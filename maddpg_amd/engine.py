@@ -36,7 +36,10 @@ class Engine:
                  gamma=0.95, tau=1e-2, grad_clip=0.5, actor_reg=1e-3, adam_b1=0.9, adam_b2=0.999,
                  adam_eps=1e-8, seed=0, world_size=1, rank=0, device=None, episode_log_rows=0,
                  prioritized=False, per_alpha=0.6, per_beta0=0.4, per_beta_inc=0.001, per_eps=0.01,
-                 per_abs_err_upper=1.0):
+                 per_abs_err_upper=1.0, act_dims=None):
+        """act_dims: per-agent action widths A_i in 1..5 (Discrete(A_i)); None: 5 for
+        every agent, or the scenario's own.  The device keeps every action slot 5
+        wide with zero pad entries; this class pads and slices at its boundary."""
         self.lib = _lib.load()
         if not torch.cuda.is_available():
             raise RuntimeError("maddpg_amd runs on a ROCm GPU only (no CPU fallback)")
@@ -91,6 +94,23 @@ class Engine:
             self.lib.mdp_destroy(h)
             self.h = None
             raise ValueError(f"mdp_create failed: {msg}")
+        dims = (ctypes.c_int32 * _lib.MAX_AGENTS)()
+        if act_dims is not None:
+            if len(act_dims) != n:
+                self.close()
+                raise ValueError(f"act_dims has {len(act_dims)} entries for {n} agents")
+            for i in range(n):
+                dims[i] = int(act_dims[i])
+            rc = self.lib.mdp_set_act_dims(self.h, dims)
+            if rc != 0:
+                msg = self.lib.mdp_last_error(self.h).decode()
+                self.close()
+                raise ValueError(msg)
+        if hasattr(self.lib, "mdp_get_act_dims"):
+            self._c("mdp_get_act_dims", dims)
+            self.act_dims = [int(dims[i]) for i in range(n)]
+        else:   # an older build chosen with MDP_LIB (A/B): every width is 5 there
+            self.act_dims = [_lib.ACT_DIM] * n
         lay = (ctypes.c_int32 * 6)()
         self.row_layout = []
         for i in range(n):
@@ -172,6 +192,42 @@ class Engine:
         start = infos[0][0]
         end = infos[5][0] + ((infos[5][3] * infos[5][4] + 3) // 4) * 4
         return self.region("grad")[start:end]
+
+    # ------------------------------------------------------- action widths
+    def set_act_dims(self, act_dims):
+        """mdp_set_act_dims on this handle (refused once it has been used)"""
+        dims = (ctypes.c_int32 * _lib.MAX_AGENTS)(*[int(a) for a in act_dims])
+        self._c("mdp_set_act_dims", dims)
+
+    def pad_act(self, agent, a):
+        """[..., A_i] -> the device's [..., 5] slot with zero pad entries; an array
+        that is already 5 wide passes as it is"""
+        A, w = _lib.ACT_DIM, self.act_dims[agent]
+        if a.shape[-1] == A:
+            return a
+        if a.shape[-1] != w:
+            raise ValueError(f"agent {agent}: last dimension {a.shape[-1]}, its action width is {w}")
+        out = a.new_zeros(a.shape[:-1] + (A,))
+        out[..., :w] = a
+        return out
+
+    def cin_columns(self, agent):
+        """device column of every logical column of agent's critic input
+        concat(obs_n + act_n) (or obs_i + act_i for a DDPG critic)"""
+        A = _lib.ACT_DIM
+        if self.local_q[agent]:
+            o = self.obs_dims[agent]
+            return list(range(o + self.act_dims[agent]))
+        so = sum(self.obs_dims)
+        cols = list(range(so))
+        for j in range(self.n):
+            cols += [so + A * j + k for k in range(self.act_dims[j])]
+        return cols
+
+    def get_grads(self, agent):
+        """{'actor': .., 'critic': ..}: the reduced gradients of agent's last update
+        (logical shapes, as get_params)"""
+        return {"actor": self.get_params(agent, "g_actor"), "critic": self.get_params(agent, "g_critic")}
 
     # ---------------------------------------------------------- parameters
     def _flat_shapes(self, agent, which):
@@ -449,14 +505,20 @@ class Engine:
 
     # ------------------------------------------------------------ policies
     def act(self, agent, obs, target=False, u=None):
+        """[rows, A_i] Gumbel-softmax samples; u: injected uniforms [rows, A_i] (or [rows, 5])"""
         obs = obs.to(self.device, torch.float32).contiguous()
         out = torch.empty((obs.shape[0], _lib.ACT_DIM), dtype=torch.float32, device=self.device)
         if u is not None:
-            u = u.to(self.device, torch.float32).contiguous()
+            u = self.pad_act(agent, u.to(self.device, torch.float32)).contiguous()
+            self._sized("u", u, obs.shape[0] * _lib.ACT_DIM)
         self.sync_in()
         self._c("mdp_act", agent, 1 if target else 0, self._ptr(obs), self._ptr(out), obs.shape[0], self._ptr(u))
         self.sync_out()
-        return out
+        return self._narrow(agent, out)
+
+    def _narrow(self, agent, out):
+        w = self.act_dims[agent]
+        return out if w == _lib.ACT_DIM else out[:, :w].contiguous()
 
     def actor_logits(self, agent, obs, target=False):
         obs = obs.to(self.device, torch.float32).contiguous()
@@ -464,10 +526,21 @@ class Engine:
         self.sync_in()
         self._c("mdp_actor_logits", agent, 1 if target else 0, self._ptr(obs), self._ptr(out), obs.shape[0])
         self.sync_out()
-        return out
+        return self._narrow(agent, out)
 
     def q_values(self, agent, x, target=False):
-        x = x.to(self.device, torch.float32).contiguous()
+        """x: the critic input in its logical width (A_j columns per action), or in
+        the device's (5 per action, pad columns zero)"""
+        x = x.to(self.device, torch.float32)
+        cols = self.cin_columns(agent)
+        dev_w = self._tensors[(agent, 1)][0][3]
+        if x.shape[1] != dev_w:
+            if x.shape[1] != len(cols):
+                raise ValueError(f"critic input of agent {agent} is {len(cols)} wide, got {x.shape[1]}")
+            xd = x.new_zeros((x.shape[0], dev_w))
+            xd[:, cols] = x
+            x = xd
+        x = x.contiguous()
         out = torch.empty(x.shape[0], dtype=torch.float32, device=self.device)
         self.sync_in()
         self._c("mdp_q_values", agent, 1 if target else 0, self._ptr(x), self._ptr(out), x.shape[0])
@@ -721,15 +794,19 @@ class Engine:
     def n_entities(self):
         """agents + landmarks (scenario make_world)."""
         landmarks = {"simple": 1, "simple_spread": self.n, "simple_adversary": self.n - 1,
-                     "simple_tag": 2}.get(self.scenario, 0)
+                     "simple_tag": 2, "simple_speaker_listener": 3}.get(self.scenario, 0)
         return self.n + landmarks
 
     def env_reset(self):
         self._c("mdp_env_reset")
 
     def env_step(self, act_in=None, u=None):
+        """act_in / u: [E, n, 5] injected actions / uniforms (a narrower agent's pad
+        entries of act_in must be zero: pad_act)"""
         a = None if act_in is None else act_in.to(self.device, torch.float32).contiguous()
         uu = None if u is None else u.to(self.device, torch.float32).contiguous()
+        self._sized("act_in", a, self.num_envs * self.n * _lib.ACT_DIM)
+        self._sized("u", uu, self.num_envs * self.n * _lib.ACT_DIM)
         if a is not None or uu is not None:
             self.sync_in()
         self._c("mdp_env_step", self._ptr(a), self._ptr(uu))
@@ -756,9 +833,11 @@ class Engine:
         self._c("mdp_env_get_state", _lib.fptr(pos), _lib.fptr(vel),
                 goal.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
                 step.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)))
-        return {"pos": pos, "vel": vel, "goal": goal, "ep_step": step}
+        comm = np.empty((E, self.n, _lib.ACT_DIM), np.float32)
+        self._c("mdp_env_get_comm", _lib.fptr(comm))
+        return {"pos": pos, "vel": vel, "goal": goal, "ep_step": step, "comm": comm}
 
-    def set_env_state(self, pos, vel, goal=None, ep_step=None):
+    def set_env_state(self, pos, vel, goal=None, ep_step=None, comm=None):
         E = self.num_envs
         pos = np.ascontiguousarray(pos, np.float32)
         vel = np.ascontiguousarray(vel, np.float32)
@@ -767,6 +846,10 @@ class Engine:
         self._c("mdp_env_set_state", _lib.fptr(pos), _lib.fptr(vel),
                 goal.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
                 ep_step.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)))
+        if comm is not None:    # [E, n, 5] state.c (scenarios with a speaking agent)
+            comm = np.ascontiguousarray(comm, np.float32)
+            assert comm.shape == (E, self.n, _lib.ACT_DIM)
+            self._c("mdp_env_set_comm", _lib.fptr(comm))
 
     def env_obs(self):
         out = torch.empty((self.num_envs, sum(self.obs_dims)), dtype=torch.float32, device=self.device)

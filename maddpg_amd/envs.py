@@ -28,10 +28,15 @@ class ScenarioSpec:
     n_agents: int
     num_adversaries: int
     obs_dims: List[int] = field(default_factory=list)
+    act_dims: List[int] = field(default_factory=list)   # Discrete(A_i) per agent; empty: Discrete(5) each
+
+    def __post_init__(self):
+        if not self.act_dims:
+            self.act_dims = [ACT_DIM] * self.n_agents
 
     @property
     def action_space(self):
-        return [Discrete(ACT_DIM) for _ in range(self.n_agents)]
+        return [Discrete(a) for a in self.act_dims]
 
     @property
     def observation_shapes(self):
@@ -57,6 +62,10 @@ def spec(name, n_agents=None, num_adversaries=None):
         L = 2
         dims = [4 + 2 * L + 2 * (n - 1) + 2 * (ng if i < na else ng - 1) for i in range(n)]
         return ScenarioSpec(name, n, na, dims)
+    if name == "simple_speaker_listener":
+        # the speaker (agent 0) sees the goal colour and says one of dim_c = 3 words; the
+        # listener sees its velocity, the 3 landmarks and the word (restated: parity UNPINNED)
+        return ScenarioSpec(name, 2, 0, [3, 11], [3, 5])
     raise ValueError(f"unknown scenario {name!r}")
 
 
@@ -72,4 +81,6 @@ def bench_record(sp, row, i):
         return tuple(float(x) for x in row[:sp.n_agents])   # n-1 landmarks + goal
     if sp.name == "simple_tag":
         return int(round(row[0]))
+    if sp.name == "simple_speaker_listener":
+        raise AttributeError("simple_speaker_listener: upstream's benchmark_data raises (undefined name)")
     raise AttributeError(f"scenario {sp.name!r} has no benchmark_data")

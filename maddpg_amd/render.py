@@ -35,6 +35,11 @@ def entity_table(sp):
     if sp.name == "simple_tag":
         ents = [(0.075, ADVERSARY) if i < na else (0.05, GOOD_TAG) for i in range(n)]
         return ents + [(0.2, LANDMARK)] * 2
+    if sp.name == "simple_speaker_listener":
+        # landmark l: 0.65 in colour component l, 0.15 elsewhere; the listener takes its
+        # goal's colour brightened upstream (here: the goal landmark is drawn in GOAL)
+        lm = [tuple(0.65 if c == l else 0.15 for c in range(3)) for l in range(3)]
+        return [(0.075, (0.25, 0.25, 0.25)), (0.075, AGENT)] + [(0.04, c) for c in lm]
     raise ValueError(sp.name)
 
 

@@ -59,9 +59,14 @@ class MADDPGAgentTrainer(AgentTrainer):
         self.act_space_n = act_space_n
         self.local_q_func = local_q_func
         check_model(model, args.num_units)
+        # one Discrete(k) space per agent, k in 1..5 (make_pdtype, distributions.py:413-415;
+        # the reference raises on anything else: its MultiDiscrete branch is commented out)
+        self.act_dims = []
         for sp in act_space_n:
-            if getattr(sp, "n", 5) != 5:
-                raise NotImplementedError("only Discrete(5) MPE action spaces are supported")
+            k = getattr(sp, "n", 5)
+            if not isinstance(k, (int, np.integer)) or not 1 <= int(k) <= 5:
+                raise NotImplementedError(f"action space {sp!r}: only Discrete(k), 1 <= k <= 5, is supported")
+            self.act_dims.append(int(k))
         self.session = U.get_session()
         self.session.register(self)
         self.replay_buffer = ReplayBuffer(1e6, _session=self.session, _agent=agent_index)
@@ -85,10 +90,10 @@ class MADDPGAgentTrainer(AgentTrainer):
         obs_n, act_n = list(arrays[:n]), list(arrays[n:2 * n])
         i = self.agent_index
         if self.local_q_func:                                          # maddpg.py:86-87
-            x = np.concatenate([np.asarray(obs_n[i], np.float32), np.asarray(act_n[i], np.float32)], 1)
+            x = [np.asarray(obs_n[i], np.float32), np.asarray(act_n[i], np.float32)]
         else:                                                          # :85
-            x = np.concatenate([np.asarray(a, np.float32) for a in obs_n + act_n], 1)
-        return self._eng().q_values(i, self._t(x), target=target).cpu().numpy()
+            x = [np.asarray(a, np.float32) for a in obs_n + act_n]
+        return self._eng().q_values(i, self._t(np.concatenate(x, 1)), target=target).cpu().numpy()
 
     # ------------------------------------------------------------ surface
     def action(self, obs):

@@ -75,7 +75,9 @@ class ReplayBuffer(object):
         for r, (p, ob, a, rw, ob1, d) in enumerate(self._pending):
             pos[r] = p
             cols[r, :o] = np.asarray(ob, np.float32).ravel()
-            cols[r, o:o + ACT] = np.asarray(a, np.float32).ravel()
+            a = np.asarray(a, np.float32).ravel()    # A_i wide (Discrete(A_i)): the slot's pad entries are zero
+            cols[r, o:o + ACT] = 0.0
+            cols[r, o:o + a.size] = a
             cols[r, o + ACT:2 * o + ACT] = np.asarray(ob1, np.float32).ravel()
             cols[r, 2 * o + ACT] = rw
             cols[r, 2 * o + ACT + 1] = d
@@ -126,7 +128,8 @@ class ReplayBuffer(object):
         rows = eng.sample_rows(idx).cpu().numpy()
         oo, ao, no, ro, do, _stride = eng.row_layout[self._agent]
         o = eng.obs_dims[self._agent]
-        return (rows[:, oo:oo + o].astype(np.float64), rows[:, ao:ao + ACT].astype(np.float32),
+        aw = eng.act_dims[self._agent]
+        return (rows[:, oo:oo + o].astype(np.float64), rows[:, ao:ao + aw].astype(np.float32),
                 rows[:, ro].astype(np.float64), rows[:, no:no + o].astype(np.float64),
                 rows[:, do].astype(np.float64))
 

@@ -1994,7 +1994,9 @@ int mdp_agent_update(mdp_handle* h, int32_t agent, int64_t t, const int32_t* idx
 // ahead: the draw runs one agent ahead instead -- agent i's launches draw
 // agent i+1's B indices of THIS round into idx (which the caller then owns),
 // the last agent's the next round's agent 0 into pf_out (ahead 1: in the fast
-// critic launches) or draw_out (ahead 2: in the optimizer launches), if any:
+// critic launches) or draw_out (ahead 2: in the optimizer launches -- halves in
+// the critic and the actor one, or all B in the critic one where the actor
+// launch between them already reads them for the next agent's critic_pre), if any:
 // the MT19937 stream order of the reference's per-agent make_index calls
 // (maddpg.py:173), with only agent 0's B of a step's first round left to the
 // rollout's draw workgroup
@@ -2020,7 +2022,11 @@ static int round_updates(mdp_handle* h, const int32_t* idx, int32_t* pf_out = nu
     if (ahead == 2) {
       dp.out = i + 1 < n ? cur + (int64_t)(i + 1) * B : draw_out;
       if (dp.out) {
-        dp.n_critic = (B + 1) / 2;
+        // agent i's actor launch runs agent i + 1's critic_pre on these indices
+        // (below): then all B of them exist before it -- the critic optimizer
+        // launch draws the whole piece (the same stream order), the actor one none
+        const bool early = i + 1 < n && critic_pre_ok(h, i, i + 1);
+        dp.n_critic = early ? B : (B + 1) / 2;
         dp.n_actor = B - dp.n_critic;
       }
     } else if (draw_out) {

@@ -452,10 +452,9 @@ def test_throughput_mode_device_noise_is_pinned_philox(monkeypatch, dims, local_
     _throughput_round_parity(monkeypatch, dims, local_q, B, H, general, device_noise_key=0x5EED5EED00C0FFEE)
 
 
-def _throughput_round_parity(monkeypatch, dims, local_q, B, H, general, device_noise_key=None):
+def _throughput_round_parity(monkeypatch, dims, local_q, B, H, general, device_noise_key=None, L=3000):
     if general:
         monkeypatch.setenv("MDP_GENERAL_GRADS", "1")
-    L = 3000
     c = synthetic_trainer_case(dims, B, L, seed=61, local_q=local_q, H=H)
     if device_noise_key is not None:
         _philox_case_noise(c, len(dims), B, device_noise_key)
@@ -543,6 +542,86 @@ def _throughput_round_parity(monkeypatch, dims, local_q, B, H, general, device_n
     eng.update_round()
     eng.synchronize()
     assert all(np.all(np.isfinite(eng.stats(i))) for i in range(n))
+
+
+# ------------------------------------------------ batch sizes off the usual list
+# nwg = ceil(B / 16) partial-gradient rows per net.  The batch reductions branch
+# on it: the 256-thread k_reduce_apply serves nwg <= 64, the 1024-thread one sums
+# partials w = grp + 16 k behind guards w < nwg (all true at B = 4096) and has a
+# tail loop from w = 256; k_reduce has the ranges w < 64, 64 <= w < 256 and its
+# own tail loop.  B = 1040: nwg = 65, the first 1024-thread launch; 2008: 126,
+# a ragged last tile; 4112: 257, the first trip of the tail loops; 5000: 313,
+# ragged again -- the gradient kernels beyond B = 4096 too.
+ADV = ([8, 10, 10], [True, False, False])     # a DDPG adversary + two MADDPG agents
+ONE = ([4], None)
+
+
+def _branch_id(v):
+    return str(v) if isinstance(v, (int, str)) else f"n{len(v[0])}"
+
+
+def _path_env(monkeypatch, path, dims, local_q, B):
+    """the environment of one launch path, and proof that the configuration takes it"""
+    if path == "general":
+        monkeypatch.setenv("MDP_GENERAL_GRADS", "1")
+    if path == "unfused":
+        monkeypatch.setenv("MDP_UNFUSED_APPLY", "1")
+    probe = Engine(dims, local_q, batch_size=B, capacity=B)
+    want = 0 if path == "general" else 1
+    assert [probe.lib.mdp_grad_variant(probe.h, i) for i in range(len(dims))] == [want] * len(dims)
+    probe.close()
+
+
+@pytest.mark.parametrize("B,cfg,path", [
+    (1040, ADV, "fast"), (2008, ONE, "fast"), (4112, ADV, "fast"), (5000, ADV, "fast"),
+    (1040, ONE, "general"), (2008, ADV, "general"), (4112, ADV, "general"), (5000, ONE, "general"),
+    (1040, ADV, "unfused"), (2008, ADV, "unfused"), (4112, ONE, "unfused"), (5000, ADV, "unfused"),
+], ids=_branch_id)
+def test_update_parity_batch_size_branches(monkeypatch, B, cfg, path):
+    """One strict round against the oracle at the batch sizes above, on the
+    register-resident kernels with the fused optimizer step (fast), on the
+    general kernels (MDP_GENERAL_GRADS=1) and on k_reduce + k_apply
+    (MDP_UNFUSED_APPLY=1), at _update_parity's unchanged tolerances (gradient
+    1e-5 of its scale, conditioned weights 1e-6, every weight 2e-4, loss 1e-5).
+    Observed on MI355X, worst over the twelve cases: gradient 2.4e-6 of its
+    scale (B = 5000), conditioned weight 1.8e-7, any weight 2.1e-6."""
+    dims, local_q = cfg
+    _path_env(monkeypatch, path, dims, local_q, B)
+    _update_parity(dims, B=B, L=4 * B, seed=B, local_q=local_q)
+
+
+@pytest.mark.parametrize("B,cfg,path", [
+    (1040, ADV, "fast"), (4112, ADV, "fast"), (5000, ONE, "fast"),
+    (2008, ADV, "general"), (4112, ONE, "general"), (5000, ADV, "general"),
+], ids=_branch_id)
+def test_throughput_mode_batch_size_branches(monkeypatch, B, cfg, path):
+    """test_throughput_mode_round_parity's body (update_all vs
+    oracle.trainer.update_round_throughput, the same tolerances) at those batch
+    sizes: k_reduce_apply_batch's 1024-thread body, every agent's gradients in
+    one launch of n * nwg workgroups (fast) and k_grad_pair (general).
+    Observed on MI355X, worst over the six cases: gradient 2.5e-7 of its
+    scale (against the fp64 restatement), conditioned weight 8.9e-8, any
+    weight 7.2e-6."""
+    dims, local_q = cfg
+    _path_env(monkeypatch, path, dims, local_q, B)
+    _throughput_round_parity(monkeypatch, dims, local_q, B, 64, path == "general", L=4 * B)
+
+
+def test_update_parity_device_noise_b2008():
+    """the device's own Philox noise in a strict round at B = 2008 (rows past
+    the last full tile draw their own counters).  Observed on MI355X: gradient
+    1.1e-6 of its scale, conditioned weight 2.2e-7, any weight 6.3e-7."""
+    dims, local_q = ADV
+    _update_parity(dims, B=2008, L=4 * 2008, seed=40 + 2008, local_q=local_q, device_noise_key=0xC0FFEE0123456789)
+
+
+def test_throughput_mode_device_noise_b5000(monkeypatch):
+    """... and in a throughput round at B = 5000 (agent i at counter upd_ctr + i).
+    Observed on MI355X: gradient 1.6e-7 of its scale, conditioned weight 7.5e-8,
+    any weight 4.5e-7."""
+    dims, local_q = ADV
+    _throughput_round_parity(monkeypatch, dims, local_q, 5000, 64, False, device_noise_key=0x5EED5EED00C0FFEE,
+                             L=4 * 5000)
 
 
 def test_throughput_grad_pair_bit_identical(monkeypatch):
@@ -943,6 +1022,51 @@ def test_train_step_graph_equals_step_then_rounds(monkeypatch, scenario, adv_pol
             for key in pa:
                 np.testing.assert_array_equal(pa[key], pb[key])
     np.testing.assert_array_equal(a.eng.replay_rows(0, 2000).cpu().numpy(), b.eng.replay_rows(0, 2000).cpu().numpy())
+    assert a.eng.buffer_len() == b.eng.buffer_len()
+    np.testing.assert_array_equal(a.eng.get_rng_state(), b.eng.get_rng_state())
+
+
+def test_train_step_graph_equals_step_then_rounds_b2008():
+    """test_train_step_graph_equals_step_then_rounds at B = 2008 (nwg = 126):
+    graph replay of the 1024-thread k_reduce_apply with part of its guards
+    false, and the fast kernels WITHOUT the next round's draw in agent 0's
+    critic launch (3 x 2008 > 4096 indices: prefetch_ok is false) -- the same
+    work as env_step + k x update_round, bit for bit, after 3 steps of 4 rounds.
+    The draw then runs one agent ahead in the optimizer launches, and agent
+    i's actor launch starts agent i + 1's critic step (critic_pre) on those
+    indices: all B of them must be drawn by agent i's critic optimizer launch.
+    (Drawn in two halves around the actor launch, as they once were, the
+    critic_pre gathered its second half from stale indices: weights differed
+    from the eager rounds by 1.5e-3 after these three steps.)"""
+    from maddpg_amd.runner import VecRunner
+    B = 2008
+
+    def make():
+        r = VecRunner("simple_spread", 64, batch_size=B, capacity=3 * B, seed=3, train_every=16, max_episode_len=2)
+        assert r.eng.lib.mdp_grad_variant(r.eng.h, 0) == 1
+        r.prefill()
+        return r
+
+    a, b = make(), make()
+    for _ in range(3):
+        t0 = a.train_step
+        k = a.step()                      # world 1: mdp_train_step
+        assert k == 4
+        b.rollout()
+        assert b.due_rounds(t0, b.train_step) == k
+        for _ in range(k):
+            b.train_round()
+    a.eng.synchronize()
+    b.eng.synchronize()
+    for i in range(a.n):
+        for w in ("actor", "critic", "tgt_actor", "tgt_critic", "m_actor", "v_critic"):
+            pa, pb = a.eng.get_params(i, w), b.eng.get_params(i, w)
+            for key in pa:
+                np.testing.assert_array_equal(pa[key], pb[key])
+        np.testing.assert_array_equal(a.eng.stats(i), b.eng.stats(i))
+        assert np.all(np.isfinite(a.eng.stats(i)))
+    n_rows = a.eng.buffer_len()
+    np.testing.assert_array_equal(a.eng.replay_rows(0, n_rows).cpu().numpy(), b.eng.replay_rows(0, n_rows).cpu().numpy())
     assert a.eng.buffer_len() == b.eng.buffer_len()
     np.testing.assert_array_equal(a.eng.get_rng_state(), b.eng.get_rng_state())
 

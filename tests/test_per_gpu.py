@@ -65,6 +65,37 @@ def test_tree_and_sampler_bit_exact(cap, B):
     assert info["samples"] == k and info["total"] == want[1, 0] and info["p_min"] == want[1, 1]
 
 
+@pytest.mark.parametrize("count", [257, 1000, 2048])
+def test_sampler_bit_exact_over_several_workgroups(count):
+    """k_per_sample runs ceil(count / 256) workgroups per agent: two with the
+    second holding one sample, four with a ragged last one, eight full ones.
+    Injected uniforms and the device's own draw give the oracle's positions and
+    weights, and the LAST workgroup to finish advances beta and the sample
+    counter once per call, not once per workgroup."""
+    cap, seed = 4096, 0x0BAD_5EED_1234
+    rng = np.random.default_rng(count)
+    eng = _engine(cap, seed=seed)
+    P = po.tree_leaves(cap)
+    prio = (rng.uniform(0.02, 1.0, cap).astype(F32) ** F32(2.5)).astype(F32)
+    _set(eng, 0, np.arange(cap), prio)
+    want = po.build(prio, P)
+    assert _same_bits(eng.per_tree(0), want)
+    k = 0
+    draws = [np.minimum(rng.uniform(0, 1, count).astype(F32), TOP), None, np.zeros(count, F32),
+             np.full(count, TOP, F32), None]
+    for u in draws:
+        idx, w = eng.per_sample(0, count, u=None if u is None else torch.from_numpy(u))
+        if u is None:                                           # the device's own Philox draw of call k
+            u = po.device_uniforms(seed, 0, k, count)
+        k += 1
+        idx, w = idx.cpu().numpy(), w.cpu().numpy()
+        assert (idx == po.sample(want, count, u)).all(), k
+        np.testing.assert_allclose(w, po.weights(want, idx, po.beta_after(k)), rtol=2e-6)
+        info = eng.per_info(0)
+        assert info["samples"] == k and info["beta"] == po.beta_after(k), (k, info)
+    assert _same_bits(eng.per_tree(0), want)                    # sampling writes no node
+
+
 @pytest.mark.parametrize("cap", [37, 4096])
 def test_partial_fill_one_leaf_equal_priorities_and_repeats(cap):
     rng = np.random.default_rng(cap)
@@ -179,6 +210,7 @@ def _loaded_engine(c, dims, B, L, H, **kw):
     ([8, 10, 10], 40, 300, 64, [True, False, False]),
     ([16, 16, 16, 14], 48, 300, 64, None),
     ([8, 10, 10], 40, 300, 128, None),
+    ([8, 10, 10], 272, 1200, 64, None),      # two sampling workgroups, the second ragged (16 of 256)
 ])
 def test_weighted_update_parity(dims, B, L, H, local_q):
     from tests.test_gpu_parity import _device_grads
@@ -263,16 +295,21 @@ def _spread(E=16, cap=48, B=16, **kw):
     return VecRunner("simple_spread", E, batch_size=B, capacity=cap, seed=3, prioritized=True, **kw)
 
 
-def test_ring_sync_resets_exactly_the_rewritten_positions():
-    r = _spread()
-    eng, cap, E, P = r.eng, 48, 16, 64
+def _ring_sync_steps(cap, steps=5):
+    """env steps of E = 16 rows on a ring of `cap`: after each one every tree is
+    po.build of the expected leaves -- the step's rows at the new-row priority,
+    every other leaf as it was -- with priorities injected at random filled
+    positions in between.  Returns the ring heads the steps left."""
+    r = _spread(cap=cap)
+    eng, E, P = r.eng, 16, 64
     rng = np.random.default_rng(0)
-    ln, head = 0, 0
+    ln, head, heads = 0, 0, []
     prio = [np.zeros(cap, F32) for _ in range(3)]
-    for step in range(5):
+    for step in range(steps):
         eng.env_step()
         new = (head + np.arange(E)) % cap
         ln, head = min(cap, ln + E), (head + E) % cap
+        heads.append(head)
         for a in range(3):
             prio[a][new] = 1.0                                   # the new-row priority
             assert _same_bits(eng.per_tree(a), po.build(prio[a][:ln], P)), (step, a)
@@ -287,6 +324,43 @@ def test_ring_sync_resets_exactly_the_rewritten_positions():
         eng.env_step()
     for a in range(3):
         assert _same_bits(eng.per_tree(a), po.build(np.ones(cap, F32), P))
+    return heads
+
+
+def test_ring_sync_resets_exactly_the_rewritten_positions():
+    assert _ring_sync_steps(48) == [16, 32, 0, 16, 32]
+
+
+def test_ring_sync_new_rows_wrap_past_the_ring_end():
+    """capacity 40: the third step's rows are positions 32..39 and 0..7, the
+    fifth's 24..39 -- k_per_sync's two-run branch (n1 > 0), which the
+    capacity-48 ring (heads at multiples of 16) never takes"""
+    assert _ring_sync_steps(40) == [16, 32, 8, 24, 0]
+
+
+def test_ring_sync_env_step_and_host_rows_between_two_syncs():
+    """an env step (16 rows) and a host add_rows (5 rows) with no sync between
+    them: arrived = E + rows = 21 positions behind the head, 32..39 and 0..12
+    on a ring of 40 -- those and no others go back to the new-row priority"""
+    cap, E, P, rows = 40, 16, 64, 5
+    r = _spread(cap=cap)
+    eng = r.eng
+    rng = np.random.default_rng(1)
+    eng.env_step()
+    eng.env_step()
+    prio = [rng.uniform(0.05, 0.9, cap).astype(F32) for _ in range(3)]
+    for a in range(3):
+        _set(eng, a, np.arange(32), prio[a][:32])
+        assert _same_bits(eng.per_tree(a), po.build(prio[a][:32], P))
+    assert eng.per_info(0)["rows_synced"] == 2 * E
+    eng.env_step()                                               # head 32 -> 8: no sync of its own
+    eng.add_rows(torch.from_numpy(rng.normal(size=(rows, eng.row_stride)).astype(F32)))   # head 8 -> 13
+    assert eng.buffer_len() == cap
+    new = np.r_[32:40, 0:13]
+    for a in range(3):
+        prio[a][new] = 1.0
+        assert _same_bits(eng.per_tree(a), po.build(prio[a], P)), a
+    assert eng.per_info(0)["rows_synced"] == 2 * E + E + rows
 
 
 # ---------------------------------------------------------- graph == eager
@@ -301,9 +375,9 @@ def _fingerprint(eng):
     return out
 
 
-def _run(graphs, how):
+def _run(graphs, how, **kw):
     # (simple_spread's TD errors exceed the default clip of 1: a wide clip keeps the priorities apart)
-    r = _spread(max_episode_len=5, per_abs_err_upper=1000.0)
+    r = _spread(max_episode_len=5, per_abs_err_upper=1000.0, **kw)
     eng = r.eng
     eng.set_graphs(graphs)
     ks = [0, 0, 0, 0, 0, 2, 1, 2]
@@ -326,6 +400,19 @@ def test_graph_replay_equals_eager(how):
     # the trees moved: priorities were written back
     assert len(np.unique(a["tree0"][64:112, 0])) > 8
     assert a["beta0"][1] == 15                                   # 3 x 5 rounds, one sample call each
+
+
+@pytest.mark.parametrize("how", ["train_steps", "update_round"])
+def test_graph_replay_equals_eager_two_sample_workgroups(how):
+    """the same at B = 272: every agent's draw is two k_per_sample workgroups
+    (the second ragged), whose ticket must leave beta and the sample counter
+    the same in a replayed graph as in the eager run; the ring of 300 wraps in
+    the third repetition (3 x 128 rows)"""
+    a, b = _run(True, how, B=272, cap=300), _run(False, how, B=272, cap=300)
+    for k in a:
+        assert a[k].tobytes() == b[k].tobytes(), k
+    assert len(np.unique(a["tree0"][512:812, 0])) > 8            # priorities were written back
+    assert a["beta0"][1] == 15 and a["beta0"][0] == po.beta_after(15)
 
 
 def test_train_steps_equals_update_round():
@@ -506,4 +593,24 @@ def test_facade_ring_wrap_resets_overwritten_rows():
     add(3)                                         # positions 25, 26, 27 only
     want = np.full(cap, low, np.float32)
     want[[25, 26, 27]] = 1.0
+    assert (mem.priorities() == want).all()
+
+
+def test_facade_new_rows_wrap_past_the_ring_end():
+    """a few rows added between two syncs that cross the end of the ring (fewer than
+    the capacity: no full reset): exactly positions 30, 31, 0, 1, 2 are new"""
+    from maddpg_amd.trainer.prioritized_replay_buffer import PrioritizedReplayMemory
+    rng = np.random.default_rng(2)
+    cap = 32
+    mem = PrioritizedReplayMemory(cap)
+    add = lambda k: [mem.add(rng.normal(size=4), rng.normal(size=5), 0.0, rng.normal(size=4), False)  # noqa: E731
+                     for _ in range(k)]
+    low = po.priority_from_error(np.float32(0.05))
+    add(30)
+    mem.batch_update(list(range(30)), np.full(30, 0.05, np.float32))
+    assert len(mem) == 30 and (mem.priorities() == low).all()
+    add(5)
+    assert len(mem) == cap
+    want = np.full(cap, low, np.float32)
+    want[[30, 31, 0, 1, 2]] = 1.0
     assert (mem.priorities() == want).all()

@@ -106,7 +106,9 @@ def relu_margin_clean_idx(c, margin=1e-5, max_iter=20):
         return np.maximum(z2, 0) @ p["W3"] + p["b3"], (z1, z2)
 
     def gsm(logits, u):
-        z = logits - np.log(-np.log(u.astype(np.float64)))
+        u = u[:, :logits.shape[1]]               # an A_j-wide agent samples from its first A_j uniforms
+        with np.errstate(divide="ignore"):       # u == 0: noise +inf, probability 0
+            z = logits - np.log(-np.log(u.astype(np.float64)))
         e = np.exp(z - z.max(-1, keepdims=True))
         return e / e.sum(-1, keepdims=True)
 

@@ -208,8 +208,11 @@ def _philox_case_noise(c, n, B, key):
     c["u_act"] = [philox.uniforms5(key, (i << 8) | 0x80, i, rows) for i in range(n)]
 
 
-def _update_parity(dims, B, L, seed, local_q=None, H=64, check_round=True, device_noise_key=None):
-    c = synthetic_trainer_case(dims, B, L, seed, local_q, H)
+def _update_parity(dims, B, L, seed, local_q=None, H=64, check_round=True, device_noise_key=None, case=None,
+                   after=None):
+    """case: a prebuilt case instead of synthetic_trainer_case(dims, B, L, seed, ..);
+    after(eng): further checks on the engine once the round has passed"""
+    c = synthetic_trainer_case(dims, B, L, seed, local_q, H) if case is None else case
     n = len(dims)
     kw = {} if device_noise_key is None else {"seed": device_noise_key}
     if device_noise_key is not None:
@@ -281,6 +284,8 @@ def _update_parity(dims, B, L, seed, local_q=None, H=64, check_round=True, devic
               f"{max(r[(w, 'fp64')] for r in creport):.3e}, vs fp32-norm (TF1 reduce_sum) step "
               f"{max(r[(w, 'fp32')] for r in creport):.3e}; |norm32 - norm64| / norm64 <= "
               f"{max(r[(w, 'norm_rel_gap')] for r in creport):.3e}")
+    if after is not None:
+        after(eng)
     return worst
 
 
@@ -452,10 +457,11 @@ def test_throughput_mode_device_noise_is_pinned_philox(monkeypatch, dims, local_
     _throughput_round_parity(monkeypatch, dims, local_q, B, H, general, device_noise_key=0x5EED5EED00C0FFEE)
 
 
-def _throughput_round_parity(monkeypatch, dims, local_q, B, H, general, device_noise_key=None, L=3000):
+def _throughput_round_parity(monkeypatch, dims, local_q, B, H, general, device_noise_key=None, L=3000, case=None,
+                             after=None):
     if general:
         monkeypatch.setenv("MDP_GENERAL_GRADS", "1")
-    c = synthetic_trainer_case(dims, B, L, seed=61, local_q=local_q, H=H)
+    c = synthetic_trainer_case(dims, B, L, seed=61, local_q=local_q, H=H) if case is None else case
     if device_noise_key is not None:
         _philox_case_noise(c, len(dims), B, device_noise_key)
         c["u_tgt"], c["u_act"] = np.stack(c["u_tgt"]), np.stack(c["u_act"])
@@ -537,6 +543,8 @@ def _throughput_round_parity(monkeypatch, dims, local_q, B, H, general, device_n
           f"worst grad |diff|/max|g| = {gworst:.3e}, worst conditioned param |diff| = {cworst:.3e}")
     assert _ctl_u32(eng, CTL_UPD_CTR_OFFSET) == n           # every agent used upd_ctr + agent
     assert _ctl_u32(eng, CTL_FAULT_OFFSET) == 0
+    if after is not None:
+        after(eng)
     # strict mode again on the same handle: mode switches are clean
     eng.set_update_mode("strict")
     eng.update_round()

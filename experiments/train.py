@@ -6,7 +6,9 @@ MPE scenario step per launch, experience goes straight into the device
 replay, and every agent's ``update()`` runs in the reference's order at the
 reference cadence (one round per 100 transitions; with E=1 -- the default --
 this is exactly the reference loop).  Extra flags: ``--num-envs``, ``--seed``,
-``--num-agents``/``--scenario-adversaries`` (scenario size), ``--train-every``.
+``--num-agents``/``--scenario-adversaries`` (scenario size), ``--train-every``,
+``--evaluate`` / ``--eval-episodes`` / ``--eval-mode`` / ``--adv-load-dir``
+(device-side policy evaluation on fixed episode ids; it leaves training untouched).
 
 Episode accounting follows the reference exactly: ``len(episode_rewards)`` is
 the number of finished episodes + 1 (a new 0 entry is appended at every reset,
@@ -91,6 +93,19 @@ def parse_args(argv=None):
     parser.add_argument("--per-beta0", type=float, default=0.4, help="initial importance-sampling exponent (:150)")
     parser.add_argument("--per-beta-inc", type=float, default=0.001, help="beta increment per sample call (:151)")
     parser.add_argument("--per-eps", type=float, default=0.01, help="added to |TD error| before the clip (:148)")
+    # device-side policy evaluation (whole episodes in one launch; training state untouched)
+    parser.add_argument("--evaluate", action="store_true", default=False,
+                        help="load as --benchmark does and score the policies on evaluation episodes 0 .. "
+                             "--eval-episodes - 1 (1024 when that flag is 0); nothing trains")
+    parser.add_argument("--eval-episodes", type=int, default=0,
+                        help="training: score these many fixed evaluation episodes at every learning-curve point "
+                             "(0: off); --evaluate: episodes to score")
+    parser.add_argument("--eval-mode", choices=["sample", "mean"], default="sample",
+                        help="sample: the policies act as in training (Gumbel-softmax); mean: softmax of the "
+                             "logits without noise")
+    parser.add_argument("--adv-load-dir", type=str, default="",
+                        help="--evaluate: take the first --num-adversaries agents from this checkpoint and the rest "
+                             "from --load-dir (cross-play)")
     return parser.parse_args(argv)
 
 
@@ -191,6 +206,41 @@ def benchmark(arglist, runner, exp_name, rank):
     return runner
 
 
+def scenario_has_records(sp):
+    return sp.name not in ("simple", "simple_speaker_listener")
+
+
+def evaluate(arglist, runner, exp_name, rank):
+    """--evaluate: the loaded policies play evaluation episodes [0, M) on the
+    device (Engine.evaluate), M = --eval-episodes or 1024.  Prints every agent's
+    mean return with its standard error and, where the scenario has
+    benchmark_data, the per-episode means of the record sums; pickles returns,
+    records and summary to <benchmark-dir><exp-name>_eval.pkl."""
+    eng, sp, n = runner.eng, runner.spec, runner.n
+    M = arglist.eval_episodes if arglist.eval_episodes > 0 else 1024
+    res = eng.evaluate(M, 0, mode=arglist.eval_mode, bench=scenario_has_records(sp))
+    ret = res["returns"].cpu().numpy()
+    rec = None if res["bench"] is None else res["bench"].cpu().numpy()
+    out = {"scenario": sp.name, "mode": arglist.eval_mode, "episodes": M, "first_episode": 0,
+           "returns": ret, "bench": rec, "summary": res["summary"]}
+    if rank == 0:
+        for i in range(n):
+            sem = res["summary"]["std"][i] / np.sqrt(M)
+            print("eval agent {}: mean return {} +- {} over {} episodes".format(i, res["summary"]["mean"][i], sem, M),
+                  flush=True)
+        if rec is not None:
+            mean_rec = rec.mean(axis=0, dtype=np.float64)
+            out["bench_mean"] = mean_rec
+            for i in range(n):
+                print("eval agent {}: mean record sums per episode {}".format(i, mean_rec[i].tolist()), flush=True)
+        file_name = arglist.benchmark_dir + exp_name + '_eval.pkl'
+        os.makedirs(os.path.dirname(file_name) or ".", exist_ok=True)
+        with open(file_name, 'wb') as fp:
+            pickle.dump(out, fp)
+    runner.synchronize()
+    return runner
+
+
 def display(arglist, runner, exp_name, rank):
     """--display (train.py:150-154): the loaded policies act, nothing trains,
     every step is rendered.  Headless: env copy 0 is rasterised to
@@ -257,9 +307,13 @@ def _train(arglist, runner, exp_name, world, rank):
 
     if arglist.load_dir == "":
         arglist.load_dir = arglist.save_dir
-    if arglist.restore or arglist.benchmark or arglist.display:   # train.py:92-96
+    if arglist.restore or arglist.benchmark or arglist.display or arglist.evaluate:   # train.py:92-96
         say('Loading previous state...')
         runner.eng.load_state(arglist.load_dir)
+    if arglist.evaluate:
+        if arglist.adv_load_dir:     # cross-play: the adversaries of another checkpoint
+            runner.eng.load_state(arglist.adv_load_dir, agents=range(num_adversaries))
+        return evaluate(arglist, runner, exp_name, rank)
     if arglist.benchmark:
         return benchmark(arglist, runner, exp_name, rank)
     if arglist.display:
@@ -267,6 +321,7 @@ def _train(arglist, runner, exp_name, world, rank):
 
     E, L = arglist.num_envs, arglist.max_episode_len
     curve = LearningCurve(arglist.save_rate, arglist.num_episodes, n)
+    eval_curve = []      # --eval-episodes: per curve point, every agent's mean return on the fixed ids
     t_start = time.time()
     t_run = time.perf_counter()
     vec_steps = 0
@@ -300,9 +355,19 @@ def _train(arglist, runner, exp_name, world, rank):
                 print("steps: {}, episodes: {}, mean episode reward: {}, agent episode reward: {}, time: {}".format(
                     steps, length, mean_ep, mean_ag, round(time.time() - t_start, 3)), flush=True)
             t_start = time.time()
+        if arglist.eval_episodes > 0 and rank == 0:
+            # the same ids every time: checkpoints compared on identical start states
+            ev = runner.evaluate(arglist.eval_episodes, 0, mode=arglist.eval_mode)["summary"] if points else None
+            for length, _, _ in points:
+                eval_curve.append(ev["mean"])
+                print("eval: episodes: {}, eval episodes: {}, mean return: {}, std: {}".format(
+                    length, arglist.eval_episodes, ev["mean"], ev["std"]), flush=True)
         if curve.done:
             if rank == 0:
                 os.makedirs(arglist.plots_dir, exist_ok=True)
+                if arglist.eval_episodes > 0:
+                    with open(arglist.plots_dir + exp_name + '_eval_rewards.pkl', 'wb') as fp:
+                        pickle.dump(eval_curve, fp)
                 with open(arglist.plots_dir + exp_name + '_rewards.pkl', 'wb') as fp:
                     pickle.dump(curve.final_ep_rewards, fp)
                 with open(arglist.plots_dir + exp_name + '_agrewards.pkl', 'wb') as fp:

@@ -17,7 +17,8 @@
  *    library's one device allocation of its own is the direct xGMI exchange
  *    buffer (mdp_dp_xgmi_open: hipExtMallocWithFlags, uncached, IPC-exported,
  *    [2 slots][world][params + probe] 64-bit words; freed by
- *    mdp_dp_xgmi_close / mdp_destroy).
+ *    mdp_dp_xgmi_close / mdp_destroy); mdp_eval_initial_state stages its
+ *    result through a temporary device buffer that it frees before returning.
  *  - "_dev" pointers are device pointers on the handle's device; "_host"
  *    pointers are host memory.  Device-pointer calls are asynchronous on the
  *    handle's stream unless stated; host-pointer calls synchronise.  Every
@@ -351,6 +352,43 @@ int mdp_env_obs(mdp_handle* h, float* obs_dev);   /* current obs [E][sum obs] */
  *   simple           has no benchmark_data (the reference's make_env raises): error */
 #define MDP_BENCH_W 8
 int mdp_env_step_bench(mdp_handle* h, float* info_dev);
+/* the same with injected Gumbel uniforms u_dev [E][n][5] (NULL: mdp_env_step_bench) */
+int mdp_env_step_bench_u(mdp_handle* h, float* info_dev, const float* u_dev);
+
+/* ---- policy evaluation: whole episodes in one launch --------------------
+ * Scores the handle's current actors on evaluation episodes without touching
+ * anything training uses.  Episode id g (32 bits) is a pure function of the
+ * actor parameters, cfg.seed, the scenario, g and the mode -- not of num_envs,
+ * of how ids are split over calls, or of the training env state:
+ *   reset     reset_world from Philox stream 0x60000, counter 0, env g (the
+ *             slot order of mdp_env_reset); ep_step 0, every state.c 0
+ *   step t    0 .. max_episode_len - 1, each mdp_env_step's step: observations
+ *             (the speaker's message is its action of step t - 1), every actor's
+ *             forward, the actions, World.step, the rewards, the records
+ *   actions   MDP_EVAL_SAMPLE: the reference's act (Gumbel-softmax) on uniforms
+ *             of stream 0x70000 | agent, counter t, row g, or injected ones;
+ *             MDP_EVAL_MEAN: the softmax of the logits without noise (the same
+ *             width-aware routine: pad entries exactly 0)
+ *   ret       [i][j] agent j's return of id first_episode + i: the fp32 sum of its
+ *             step rewards in step order (collaborative scenarios: the shared sum)
+ *   bench     [i][j][MDP_BENCH_W] the fp32 sum in step order of the record
+ *             mdp_env_step_bench writes; refused where that call is refused
+ * It neither reads nor writes the training env state, the replay ring, the
+ * episode log, the comm state, any control field (env step / episode counters,
+ * tickets, the index RNG, the noise counter) or the prioritized-replay buffer.
+ * One workgroup per 16 ids carries them through the whole episode.
+ * ids [first_episode, first_episode + episodes): 1 <= episodes <= 2^20, the range inside uint32.
+ * u_dev: NULL or [episodes][max_episode_len][n_agents][5] uniforms (SAMPLE only);
+ * ret_dev [episodes][n_agents]; bench_dev NULL or [episodes][n_agents][MDP_BENCH_W].
+ * Refused with a message before any launch: a bad mode, count or id range, u_dev
+ * with MDP_EVAL_MEAN, a call while the handle's stream is capturing a graph. */
+enum { MDP_EVAL_SAMPLE = 0, MDP_EVAL_MEAN = 1 };
+int mdp_evaluate(mdp_handle* h, int64_t first_episode, int32_t episodes, int32_t mode,
+                 const float* u_dev, float* ret_dev, float* bench_dev);
+/* the start states of those ids: pos/vel [episodes][n_entities][2], goal [episodes]
+ * (host, synchronises; staged through a temporary device buffer freed before return) */
+int mdp_eval_initial_state(mdp_handle* h, int64_t first_episode, int32_t episodes,
+                           float* pos_host, float* vel_host, int32_t* goal_host);
 /* finished-episode log: total entries written so far, copy last `n` [n][1+n_agents] */
 int64_t mdp_episode_count(mdp_handle* h);
 int mdp_episode_log(mdp_handle* h, int64_t first, int64_t n, float* out_host);
@@ -433,7 +471,8 @@ enum mdp_kernel_kind {
     MDP_K_APPLY = 4, MDP_K_ROLLOUT = 5, MDP_K_REDUCE = 6, MDP_K_REDUCE_APPLY = 7,
     MDP_K_ALLREDUCE = 8,   /* the RCCL data-parallel all-reduces (not a kernel of this library) */
     MDP_K_PER_SYNC = 9, MDP_K_PER_SAMPLE = 10, MDP_K_PER_UPDATE = 11,   /* prioritized replay (mdp_per.hip) */
-    MDP_K_COUNT = 12
+    MDP_K_EVAL = 12,       /* k_eval_episodes (mdp_evaluate) */
+    MDP_K_COUNT = 13
 };
 int mdp_prof_enable(mdp_handle* h, int32_t kind, int32_t on);
 /* which grad kernels serve `agent`: 1 = register-resident k_*_grad_r (H = 64

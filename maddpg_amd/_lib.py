@@ -34,6 +34,10 @@ KERNEL = {"index": 0, "gather": 1, "critic_grad": 2, "actor_grad": 3, "apply": 4
           "reduce": 6, "reduce_apply": 7, "allreduce": 8}
 # the prioritized-replay kernels (mdp_per.hip), timed only when asked for by name
 KERNEL_PER = {"per_sync": 9, "per_sample": 10, "per_update": 11}
+# the policy-evaluation kernel (k_eval_episodes), timed only when asked for by name
+KERNEL_EVAL = {"eval": 12}
+EVAL_MODE = {"sample": 0, "mean": 1}   # MDP_EVAL_SAMPLE / MDP_EVAL_MEAN
+EVAL_MAX_EPISODES = 1 << 20            # ids per mdp_evaluate call
 
 
 class MdpConfig(ctypes.Structure):
@@ -142,6 +146,9 @@ SIGNATURES = {
     "mdp_env_set_comm": (ctypes.c_int, [_P, _F32P]),
     "mdp_env_obs": (ctypes.c_int, [_P, _P]),
     "mdp_env_step_bench": (ctypes.c_int, [_P, _P]),
+    "mdp_env_step_bench_u": (ctypes.c_int, [_P, _P, _P]),
+    "mdp_evaluate": (ctypes.c_int, [_P, _I64, _I32, _I32, _P, _P, _P]),
+    "mdp_eval_initial_state": (ctypes.c_int, [_P, _I64, _I32, _F32P, _F32P, _I32P]),
     "mdp_set_update_mode": (ctypes.c_int, [_P, _I32]),
     "mdp_update_all": (ctypes.c_int, [_P, _P, _P, _P]),
     "mdp_episode_count": (_I64, [_P]),

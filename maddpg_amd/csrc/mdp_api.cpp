@@ -2513,6 +2513,102 @@ int mdp_env_step_bench(mdp_handle* h, float* info_dev) {
   return 0;
 }
 
+// why a scenario has no benchmark_data records (null: it has)
+static const char* no_bench_reason(int scenario) {
+  if (scenario == MDP_SCN_SIMPLE) return "scenario 'simple' has no benchmark_data (MPE Scenario attribute missing)";
+  if (scenario == MDP_SCN_SPEAKER_LISTENER)
+    return "scenario 'simple_speaker_listener': upstream's benchmark_data raises (it names an undefined "
+           "variable), so there is no record to return";
+  return nullptr;
+}
+
+int mdp_env_step_bench_u(mdp_handle* h, float* info_dev, const float* u_dev) {
+  if (need_env(h)) return -1;
+  if (!info_dev) return fail(h, "mdp_env_step_bench_u: info_dev is null");
+  const int64_t en = 4 * (int64_t)h->cfg.num_envs * h->cfg.n_agents;
+  MDP_DEV(h, info_dev, en * MDP_BENCH_W, "mdp_env_step_bench_u", false);
+  MDP_DEV(h, u_dev, en * MDP_ACT_DIM, "mdp_env_step_bench_u", true);
+  if (const char* why = no_bench_reason(h->cfg.scenario)) return fail(h, why);
+  const int rc = env_step_launch(h, nullptr, u_dev, info_dev);
+  if (rc) return rc;
+  advance_ring_mirror(h);
+  return 0;
+}
+
+// ---- policy evaluation (k_eval_episodes)
+#define MDP_EVAL_MAX_EPISODES (1 << 20)
+static int eval_range_ok(mdp_handle* h, const char* fn, int64_t first, int32_t episodes) {
+  std::string m = std::string(fn) + ": ";
+  if (episodes < 1 || episodes > MDP_EVAL_MAX_EPISODES) return fail(h, (m + "1 <= episodes <= 2^20").c_str());
+  if (first < 0 || first + episodes > ((int64_t)1 << 32))
+    return fail(h, (m + "episode ids [first_episode, first_episode + episodes) must lie inside uint32").c_str());
+  return 0;
+}
+
+int mdp_evaluate(mdp_handle* h, int64_t first_episode, int32_t episodes, int32_t mode, const float* u_dev,
+                 float* ret_dev, float* bench_dev) {
+  if (need_env(h)) return -1;
+  if (mode != MDP_EVAL_SAMPLE && mode != MDP_EVAL_MEAN)
+    return fail(h, "mdp_evaluate: mode must be MDP_EVAL_SAMPLE (0) or MDP_EVAL_MEAN (1)");
+  if (eval_range_ok(h, "mdp_evaluate", first_episode, episodes)) return -1;
+  if (u_dev && mode == MDP_EVAL_MEAN) return fail(h, "mdp_evaluate: u_dev is given but MDP_EVAL_MEAN draws no noise");
+  if (!ret_dev) return fail(h, "mdp_evaluate: ret_dev is null");
+  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+  if (h->capturing || (hipStreamIsCapturing(h->stream, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone))
+    return fail(h, "mdp_evaluate: the handle's stream is capturing a graph (evaluation is not captured)");
+  (void)hipGetLastError();
+  const int64_t en = 4 * (int64_t)episodes * h->cfg.n_agents;
+  MDP_DEV(h, u_dev, en * h->cfg.max_episode_len * MDP_ACT_DIM, "mdp_evaluate", true);
+  MDP_DEV(h, ret_dev, en, "mdp_evaluate", false);
+  MDP_DEV(h, bench_dev, en * MDP_BENCH_W, "mdp_evaluate", true);
+  if (bench_dev)
+    if (const char* why = no_bench_reason(h->cfg.scenario)) return fail(h, why);
+  EvalEpArgs a;
+  a.topo = h->L.topo;
+  a.env = h->L.env;
+  a.theta = h->theta;
+  a.seed = h->cfg.seed;
+  a.first = (uint32_t)first_episode;
+  a.episodes = episodes;
+  a.mode = mode;
+  a.u_in = u_dev;
+  a.ret = ret_dev;
+  a.bench = bench_dev;
+  ProfScope p(h, MDP_K_EVAL);
+  HIPCHK(h, mdp_launch_eval_episodes(a, h->L.topo.H, lds_rollout_bytes(h->L.topo), h->stream));
+  return 0;
+}
+
+int mdp_eval_initial_state(mdp_handle* h, int64_t first_episode, int32_t episodes, float* pos_host, float* vel_host,
+                           int32_t* goal_host) {
+  if (need_env(h)) return -1;
+  if (eval_range_ok(h, "mdp_eval_initial_state", first_episode, episodes)) return -1;
+  if (!pos_host || !vel_host || !goal_host) return fail(h, "mdp_eval_initial_state: null output");
+  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+  if (h->capturing || (hipStreamIsCapturing(h->stream, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone))
+    return fail(h, "mdp_eval_initial_state: the handle's stream is capturing a graph");
+  (void)hipGetLastError();
+  const int64_t ne2 = 2 * (int64_t)(h->L.env.n_agents + h->L.env.n_landmarks);
+  const int chunk = std::min<int64_t>(episodes, 1 << 16);  // ids staged at a time
+  float* tmp = nullptr;
+  HIPCHK(h, hipMalloc((void**)&tmp, (size_t)chunk * (2 * ne2 + 1) * 4));
+  float* dpos = tmp;
+  float* dvel = tmp + chunk * ne2;
+  int32_t* dgoal = reinterpret_cast<int32_t*>(tmp + 2 * chunk * ne2);
+  hipError_t e = hipSuccess;
+  for (int64_t done = 0; done < episodes && e == hipSuccess; done += chunk) {
+    const int c = (int)std::min<int64_t>(chunk, episodes - done);
+    e = mdp_launch_eval_reset(h->L.env, h->cfg.seed, (uint32_t)(first_episode + done), c, dpos, dvel, dgoal, h->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(pos_host + done * ne2, dpos, (size_t)c * ne2 * 4, hipMemcpyDeviceToHost, h->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(vel_host + done * ne2, dvel, (size_t)c * ne2 * 4, hipMemcpyDeviceToHost, h->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(goal_host + done, dgoal, (size_t)c * 4, hipMemcpyDeviceToHost, h->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+  }
+  (void)hipFree(tmp);
+  if (e != hipSuccess) return fail(h, "mdp_eval_initial_state", e);
+  return 0;
+}
+
 // rollout, then `rounds` rounds on alternating index slots; round r's first
 // critic kernel draws round r+1's indices (same ring length: the rounds of one
 // step follow one rollout) in an extra workgroup -- the draw leaves the

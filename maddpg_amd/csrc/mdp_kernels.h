@@ -326,6 +326,20 @@ struct EnvObsArgs {
   float* obs;
 };
 
+// k_eval_episodes: episode ids [first, first + episodes), 16 per workgroup
+struct EvalEpArgs {
+  Topo topo;
+  EnvDesc env;
+  const float* theta;
+  uint64_t seed;
+  uint32_t first;
+  int episodes;
+  int mode;            // MDP_EVAL_SAMPLE / MDP_EVAL_MEAN
+  const float* u_in;   // [episodes][max_ep_len][n][MDP_ACT_DIM] injected uniforms or null
+  float* ret;          // [episodes][n]
+  float* bench;        // [episodes][n][MDP_BENCH_W] record sums or null
+};
+
 struct EvalArgs {
   const float* P;
   NDesc net;
@@ -426,6 +440,9 @@ hipError_t mdp_launch_critic_grad_r_per(const CriticArgsPer& a, int lds_bytes, h
 hipError_t mdp_launch_actor_grad_r(const ActorArgs& a, int lds_bytes, hipStream_t s);
 hipError_t mdp_launch_rollout(const RolloutArgs& a, int H, int lds_bytes, hipStream_t s);
 hipError_t mdp_launch_eval(const EvalArgs& a, int H, int lds_bytes, hipStream_t s);
+hipError_t mdp_launch_eval_episodes(const EvalEpArgs& a, int H, int lds_bytes, hipStream_t s);
+hipError_t mdp_launch_eval_reset(const EnvDesc& env, uint64_t seed, uint32_t first, int count, float* pos, float* vel,
+                                 int32_t* goal, hipStream_t s);
 hipError_t mdp_launch_apply(const ApplyArgs& a, hipStream_t s);
 hipError_t mdp_launch_reduce(const ReduceArgs& a, hipStream_t s);
 hipError_t mdp_launch_reduce_apply(const FusedApplyArgs& f, hipStream_t s);

@@ -9,6 +9,8 @@
 //   tf_util.py:177-182 + TF ApplyAdam + maddpg.py:20-26 -> k_apply (clip, Adam, Polyak)
 //   train.py:112-128 + MPE World.step -> k_rollout (actors + Gumbel + physics + obs/reward
 //                                        + replay append + episode reset), k_env_reset
+//   train.py:139-148 (--benchmark: the policies play, nothing trains) -> k_eval_episodes
+//                                        (whole episodes per workgroup, no replay / log / Ctl)
 #include "mdp_device.h"
 #include "mdp_kernels.h"
 #include "mdp_mt.h"
@@ -1114,6 +1116,213 @@ __global__ __launch_bounds__(MDP_NT) void k_rollout(RolloutArgs a) {
   rollout_finish(a, next_raw, len_raw);
 }
 
+// Policy evaluation: whole episodes in one launch (mdp_evaluate).  A workgroup
+// carries 16 episode ids from reset_world to max_episode_len with k_rollout's
+// step -- the same device functions in the same order, so an episode's rewards
+// are bit for bit those of the k_rollout chain on the same state and uniforms --
+// but it writes no replay row, no episode log and no Ctl field, so it needs no
+// other workgroup: state, returns and the message (the speaker's action block of
+// the previous step, still in the row tile) stay in LDS between the steps, and
+// on the H = 64 one-wave-per-agent path the weight fragments stay in registers.
+// Global traffic: the weights in, ret / bench out (and injected uniforms in).
+// Episode id g = first + its index: reset stream 0x60000 (ctr 0, env g), noise
+// stream 0x70000 | agent (ctr = step, row g).
+template <int H>
+__global__ __launch_bounds__(MDP_NT) void k_eval_episodes(EvalEpArgs a) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  const Topo& T = a.topo;
+  const EnvDesc& E = a.env;
+  const int n = E.n_agents;
+  const int ldr = lds_ld(T.row_stride), ldh = H + 1;
+  LdsCarve cv(lds);  // k_rollout's carve (lds_rollout_bytes)
+  float* rowt = cv.take(MDP_R * ldr);
+  float* h1 = cv.take(MDP_R * ldh);
+  float* h2 = cv.take(MDP_R * ldh);
+  float* lg = cv.take(MDP_R * 8);
+  constexpr int PAR_W = H == 64 ? MDP_NW * (2 * MDP_R * MDP_RLH + MDP_R * 8) : 0;
+  float* hpar = cv.take(PAR_W);
+  float* sp = cv.take(MDP_R * 2 * MDP_MAX_ENT);
+  float* sv = cv.take(MDP_R * 2 * MDP_MAX_ENT);
+  float* sfo = cv.take(MDP_R * 3 * MDP_MAX_ENT);
+  float* epr = cv.take(MDP_R * MDP_MAX_AGENTS);  // the episodes' returns so far
+  int* sgoal = reinterpret_cast<int*>(cv.take(MDP_R));
+  // this step's records of the tile, [R][n][MDP_BENCH_W]: in h1, which is free
+  // between a step's forward and the next one's
+  static_assert(MDP_R * MDP_MAX_AGENTS * MDP_BENCH_W <= MDP_R * (H + 1), "record tile fits h1");
+  float* rec = h1;
+
+  const int tid = threadIdx.x;
+  const int i0 = (int)blockIdx.x * MDP_R;
+  const int nvalid = min(MDP_R, a.episodes - i0);
+  const bool comm = env_dim_c(E.scenario) > 0;
+  const bool mean = a.mode == MDP_EVAL_MEAN;
+
+  for (int q = tid; q < MDP_R * ldr; q += MDP_NT) rowt[q] = 0.f;
+  for (int q = tid; q < MDP_R * 2 * MDP_MAX_ENT; q += MDP_NT) sp[q] = sv[q] = 0.f;
+  if (tid < MDP_R * MDP_MAX_AGENTS) epr[tid] = 0.f;
+  if (tid < MDP_R) sgoal[tid] = 0;
+  __syncthreads();
+  if (tid < nvalid) {
+    int32_t g;
+    env_reset_one(E, a.seed, 0x60000u, 0u, a.first + (uint32_t)(i0 + tid), sp + tid * 2 * MDP_MAX_ENT,
+                  sv + tid * 2 * MDP_MAX_ENT, &g);
+    sgoal[tid] = g;
+  }
+
+  // the policy forward's path, as k_rollout chooses it
+  bool par = false;
+  if constexpr (H == 64) {
+    par = n <= MDP_NW;
+    for (int j = 0; j < n; ++j) par = par && T.ag[j].obs_dim <= 64;
+  }
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63, r16 = lane & 15, kq = lane >> 4;
+  // H = 64, one wave per agent: every fragment of the net loaded once for the episode
+  f32x4 w1[16], w2[16], b1 = {0.f, 0.f, 0.f, 0.f}, b2 = {0.f, 0.f, 0.f, 0.f};
+  float w3[16], b3 = 0.f;
+  if constexpr (H == 64) {
+    if (par && wave < n) {
+      const ADesc& aj = T.ag[wave];
+      const NDesc& an = aj.actor;
+      const float* P = a.theta;
+      rf_load<16>(w1, P + an.t[0].off, aj.obs_dim);
+      rf_load<16>(w2, P + an.t[2].off, MDP_RH);
+      rh_load(w3, P + an.t[4].off, MDP_ACT_DIM);
+      b1 = ld4(P + an.t[1].off + 4 * r16);
+      b2 = ld4(P + an.t[3].off + 4 * r16);
+      b3 = P[an.t[5].off + min(r16, MDP_ACT_DIM - 1)];
+    }
+  }
+  // record sums of (episode, agent) = (tid / n, tid % n), in step order
+  float bsum[MDP_BENCH_W];
+#pragma unroll
+  for (int k = 0; k < MDP_BENCH_W; ++k) bsum[k] = 0.f;
+  const int br = tid / n, bj = tid - br * n;
+  __syncthreads();
+
+  const int nst = E.max_ep_len;
+  for (int t = 0; t < nst; ++t) {
+    // the sample of (row lane, agent j): k_rollout's, or the noise-free softmax
+    auto sample = [&](const float* logits, int row, int j, float* dst) {
+      float gn[MDP_ACT_DIM];
+      if (mean) {
+#pragma unroll
+        for (int k = 0; k < MDP_ACT_DIM; ++k) gn[k] = 0.f;
+      } else {
+        float u[MDP_ACT_DIM];
+        if (a.u_in) {
+          for (int k = 0; k < MDP_ACT_DIM; ++k)
+            u[k] = row < nvalid ? a.u_in[(((int64_t)(i0 + row) * nst + t) * n + j) * MDP_ACT_DIM + k] : 0.5f;
+        } else {
+          uniforms5(a.seed, 0x70000u | (uint32_t)j, (uint32_t)t, a.first + (uint32_t)(i0 + row), u);
+        }
+        gumbel_noise5(u, gn);
+      }
+      gumbel_softmax_pre(logits, gn, dst, topo_act_w(T, j));
+    };
+    // observations, one thread per (episode, agent); the listener hears the
+    // speaker's action of the previous step (state.c; zero in the first)
+    if (tid < MDP_R * n) {
+      const int r = tid / n, j = tid - r * n;
+      if (comm)
+        env_obs_comm(E, sp + r * 2 * MDP_MAX_ENT, sv + r * 2 * MDP_MAX_ENT, sgoal[r], j, rowt + r * ldr + T.ag[j].obs_off,
+                     t > 0 ? rowt + r * ldr + T.ag[0].act_off : nullptr);
+      else
+        env_obs(E, sp + r * 2 * MDP_MAX_ENT, sv + r * 2 * MDP_MAX_ENT, sgoal[r], j, rowt + r * ldr + T.ag[j].obs_off);
+    }
+    __syncthreads();
+    if (par) {
+      if constexpr (H == 64) {
+        if (wave < n) {
+          const int j = wave;
+          const ADesc& aj = T.ag[j];
+          float* h1j = hpar + j * (2 * MDP_R * MDP_RLH + MDP_R * 8);
+          float* h2j = h1j + MDP_R * MDP_RLH;
+          float* lgj = h2j + MDP_R * MDP_RLH;
+          {
+            f32x4 acc[4];
+            rf_zero(acc);
+            rf_acc<16>(acc, rowt + aj.obs_off, ldr, aj.obs_dim, w1);
+            rf_store<true>(acc, b1, h1j, MDP_RLH);
+          }
+          wave_sync();
+          {
+            f32x4 acc[4];
+            rf_zero(acc);
+            rf_acc<16>(acc, h1j, MDP_RLH, MDP_RH, w2);
+            rf_store<true>(acc, b2, h2j, MDP_RLH);
+          }
+          wave_sync();
+          {
+            const f32x4 acc = rh_acc(h2j, MDP_RLH, w3);
+            if (r16 < MDP_ACT_DIM) {
+#pragma unroll
+              for (int i = 0; i < 4; ++i) lgj[(kq * 4 + i) * 8 + r16] = acc[i] + b3;
+            }
+          }
+          wave_sync();
+          if (lane < MDP_R) sample(lgj + lane * 8, lane, j, rowt + lane * ldr + aj.act_off);
+        }
+        __syncthreads();
+      }
+    }
+    for (int j = 0; j < (par ? 0 : n); ++j) {
+      const ADesc& aj = T.ag[j];
+      bool pf = false;
+      if constexpr (H == 64 && MDP_NW == 4) {
+        if (aj.obs_dim <= 4 * MDP_KC) {
+          mlp_fwd_tile_pf<H>(rowt + aj.obs_off, ldr, aj.obs_dim, a.theta, aj.actor, h1, h2, ldh, lg, 8);
+          pf = true;
+        }
+      }
+      if (!pf) mlp_fwd_tile<H>(rowt + aj.obs_off, ldr, aj.obs_dim, a.theta, aj.actor, h1, h2, ldh, lg, 8);
+      if (tid < MDP_R) sample(lg + tid * 8, tid, j, rowt + tid * ldr + aj.act_off);
+      __syncthreads();
+    }
+
+    env_physics_tile(E, sp, sv, rowt + T.ag[0].act_off, ldr, sfo, nvalid);
+    if (tid < nvalid) {
+      const float* p = sp + tid * 2 * MDP_MAX_ENT;
+      float* rew = rowt + tid * ldr + T.ag[0].rew_off;  // rew_0 .. rew_{n-1} are contiguous (mdp_topo.h)
+      env_reward(E, p, sgoal[tid], rew);
+      if (a.bench) env_bench(E, p, sgoal[tid], rec + tid * n * MDP_BENCH_W);
+      for (int j = 0; j < n; ++j) epr[tid * MDP_MAX_AGENTS + j] = epr[tid * MDP_MAX_AGENTS + j] + rew[j];
+    }
+    if (a.bench) {
+      __syncthreads();
+      if (tid < MDP_R * n && br < nvalid) {
+#pragma unroll
+        for (int k = 0; k < MDP_BENCH_W; ++k) bsum[k] += rec[(br * n + bj) * MDP_BENCH_W + k];
+      }
+    }
+    __syncthreads();
+  }
+
+  if (tid < MDP_R * n && br < nvalid) {
+    const int64_t o = (int64_t)(i0 + br) * n + bj;
+    a.ret[o] = epr[br * MDP_MAX_AGENTS + bj];
+    if (a.bench) {
+#pragma unroll
+      for (int k = 0; k < MDP_BENCH_W; ++k) a.bench[o * MDP_BENCH_W + k] = bsum[k];
+    }
+  }
+}
+
+// start states of episode ids [first, first + count) (mdp_eval_initial_state)
+__global__ __launch_bounds__(256) void k_eval_reset(EnvDesc env, uint64_t seed, uint32_t first, int count, float* pos,
+                                                    float* vel, int32_t* goal) {
+  const int e = blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= count) return;
+  const int ne = env.n_agents + env.n_landmarks;
+  float p[2 * MDP_MAX_ENT], v[2 * MDP_MAX_ENT];
+  int32_t g;
+  env_reset_one(env, seed, 0x60000u, 0u, first + (uint32_t)e, p, v, &g);
+  for (int q = 0; q < 2 * ne; ++q) {
+    pos[(int64_t)e * 2 * ne + q] = p[q];
+    vel[(int64_t)e * 2 * ne + q] = v[q];
+  }
+  goal[e] = g;
+}
+
 // batched policy / critic evaluation for the facade (action, target_act, q_values)
 template <int H>
 __global__ __launch_bounds__(MDP_NT) void k_mlp_eval(EvalArgs a) {
@@ -1181,6 +1390,7 @@ static void raise_lds_limits() {
   (void)hipFuncSetAttribute((const void*)k_rollout<H, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
   (void)hipFuncSetAttribute((const void*)k_rollout<H, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
   (void)hipFuncSetAttribute((const void*)k_mlp_eval<H>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
+  (void)hipFuncSetAttribute((const void*)k_eval_episodes<H>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
 }
 static void ensure_lds_limits() {
   if (!set_lds_limit_done) {
@@ -1209,6 +1419,27 @@ hipError_t mdp_launch_eval(const EvalArgs& a, int H, int lds_bytes, hipStream_t 
     case 256: return launch_eval_t<256>(a, lds_bytes, s);
     default: return hipErrorInvalidValue;
   }
+}
+template <int H>
+static hipError_t launch_eval_episodes_t(const EvalEpArgs& a, int lds_bytes, hipStream_t s) {
+  mdp_launch(k_eval_episodes<H>, dim3((a.episodes + MDP_R - 1) / MDP_R), dim3(MDP_NT), lds_bytes, s, a);
+  MDP_CHECK_LAUNCH();
+  return hipSuccess;
+}
+hipError_t mdp_launch_eval_episodes(const EvalEpArgs& a, int H, int lds_bytes, hipStream_t s) {
+  ensure_lds_limits();
+  switch (H) {
+    case 64: return launch_eval_episodes_t<64>(a, lds_bytes, s);
+    case 128: return launch_eval_episodes_t<128>(a, lds_bytes, s);
+    case 256: return launch_eval_episodes_t<256>(a, lds_bytes, s);
+    default: return hipErrorInvalidValue;
+  }
+}
+hipError_t mdp_launch_eval_reset(const EnvDesc& env, uint64_t seed, uint32_t first, int count, float* pos, float* vel,
+                                 int32_t* goal, hipStream_t s) {
+  hipLaunchKernelGGL(k_eval_reset, dim3((count + 255) / 256), dim3(256), 0, s, env, seed, first, count, pos, vel, goal);
+  MDP_CHECK_LAUNCH();
+  return hipSuccess;
 }
 hipError_t mdp_launch_apply(const ApplyArgs& a, hipStream_t s) {
   const int grid = a.blk[6] + (a.polyak ? a.oblk[6] : 0) + (a.stats_mode ? 1 : 0);

@@ -298,8 +298,11 @@ class Engine:
             out[f"agent_{i}/critic/beta_power"] = self.get_beta_powers(i, 1)
         return out
 
-    def load_state_dict(self, sd):
-        for i in range(self.n):
+    def load_state_dict(self, sd, agents=None):
+        """agents: restore only these agents' parameter sets (None: every agent)"""
+        for i in range(self.n) if agents is None else sorted({int(a) for a in agents}):
+            if not 0 <= i < self.n:
+                raise ValueError(f"agent {i} out of range for {self.n} agents")
             for w in self.SETS:
                 self.set_params(i, w, {k: sd[f"agent_{i}/{w}/{k}"] for k in TENSOR_NAMES})
             self.set_beta_powers(i, 0, sd[f"agent_{i}/actor/beta_power"])
@@ -348,8 +351,10 @@ class Engine:
         elif os.path.isfile(self.checkpoint_path(fname)):
             os.remove(self.checkpoint_path(fname))
 
-    def load_state(self, fname):
-        """Restore from a TF1 tensor bundle at prefix `fname` (the reference's
+    def load_state(self, fname, agents=None):
+        """agents: a list restores only those agents' parameter sets (cross-play of
+        two checkpoints); None restores every agent.
+        Restore from a TF1 tensor bundle at prefix `fname` (the reference's
         tf.train.Saver checkpoint, tf_util.py:259-264) or from the .npz
         save_state writes.  save_state removes the other format's files, so
         both exist only when another tool wrote one of them: then the newer
@@ -367,11 +372,12 @@ class Engine:
             use_tf1 = t_tf1 >= t_npz
         else:
             use_tf1 = tfc.is_bundle(fname)
+        more = () if agents is None else (agents,)
         if use_tf1:
-            self.load_state_dict(tfc.state_from_tf1(tfc.read_bundle(fname), self.n, self.SETS))
+            self.load_state_dict(tfc.state_from_tf1(tfc.read_bundle(fname), self.n, self.SETS), *more)
             return fname
         with np.load(path, allow_pickle=False) as z:
-            self.load_state_dict({k: z[k] for k in z.files})
+            self.load_state_dict({k: z[k] for k in z.files}, *more)
         return path
 
     # ------------------------------------------------------------- replay
@@ -814,15 +820,64 @@ class Engine:
             self._keep = (a, uu)
             self.sync_out()
 
-    def env_step_bench(self, out=None):
+    def env_step_bench(self, out=None, u=None):
         """one vector env step (policy actions) that also returns every agent's
         scenario benchmark_data() record, [E, n, BENCH_W] float32 on the device
-        (mdp_env_step_bench; --benchmark mode, train.py:139-141)."""
+        (mdp_env_step_bench; --benchmark mode, train.py:139-141).  u: [E, n, 5]
+        injected Gumbel uniforms, as env_step's."""
         if out is None:
             out = torch.empty((self.num_envs, self.n, _lib.BENCH_W), dtype=torch.float32, device=self.device)
-        self._c("mdp_env_step_bench", self._ptr(out))
+        if u is None:
+            self._c("mdp_env_step_bench", self._ptr(out))
+        else:
+            uu = u.to(self.device, torch.float32).contiguous()
+            self._sized("u", uu, self.num_envs * self.n * _lib.ACT_DIM)
+            self.sync_in()
+            self._c("mdp_env_step_bench_u", self._ptr(out), self._ptr(uu))
+            self._keep = (uu,)
         self.sync_out()
         return out
+
+    # ---------------------------------------------------------- evaluation
+    def evaluate(self, episodes, first_episode=0, mode="sample", bench=False, u=None):
+        """Score the current actors on evaluation episodes [first_episode,
+        first_episode + episodes) (mdp_evaluate): whole episodes on the device,
+        nothing training uses is read or written.  An id's result depends only
+        on the actor parameters, the seed, the scenario, the id and the mode.
+        mode "sample": the reference's act; "mean": the softmax of the logits
+        without noise.  u: [episodes, max_episode_len, n, 5] injected uniforms
+        (sample mode).  Returns a dict: `returns` [episodes, n] float32 device
+        tensor, `bench` [episodes, n, BENCH_W] record sums or None, `summary`
+        per-agent mean / population std / min / max of the returns in fp64."""
+        if mode not in _lib.EVAL_MODE:
+            raise ValueError(f"unknown evaluation mode {mode!r} (sample, mean)")
+        episodes, first_episode = int(episodes), int(first_episode)
+        uu = None if u is None else u.to(self.device, torch.float32).contiguous()
+        self._sized("u", uu, episodes * self.max_episode_len * self.n * _lib.ACT_DIM)
+        ret = torch.empty((max(episodes, 0), self.n), dtype=torch.float32, device=self.device)
+        rec = None
+        if bench:
+            rec = torch.empty((max(episodes, 0), self.n, _lib.BENCH_W), dtype=torch.float32, device=self.device)
+        self.sync_in()
+        self._c("mdp_evaluate", first_episode, episodes, _lib.EVAL_MODE[mode], self._ptr(uu), self._ptr(ret),
+                self._ptr(rec))
+        self._keep = (uu,)
+        self.sync_out()
+        r64 = ret.double()
+        summary = {"mean": r64.mean(0).tolist(), "std": r64.std(0, unbiased=False).tolist(),
+                   "min": r64.min(0).values.tolist(), "max": r64.max(0).values.tolist()}
+        return {"returns": ret, "bench": rec, "summary": summary}
+
+    def eval_initial_state(self, episodes, first_episode=0):
+        """start states of those evaluation ids (mdp_eval_initial_state): pos / vel
+        [episodes, n_entities, 2] float32, goal [episodes] int32 (host arrays)"""
+        episodes, ne = int(episodes), self.n_entities
+        pos = np.empty((max(episodes, 0), ne, 2), np.float32)
+        vel = np.empty((max(episodes, 0), ne, 2), np.float32)
+        goal = np.empty(max(episodes, 0), np.int32)
+        self._c("mdp_eval_initial_state", int(first_episode), episodes, _lib.fptr(pos), _lib.fptr(vel),
+                goal.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)))
+        return {"pos": pos, "vel": vel, "goal": goal}
 
     def env_state(self):
         E, ne = self.num_envs, self.n_entities
@@ -877,7 +932,10 @@ class Engine:
     # ---------------------------------------------------------- profiling
     @staticmethod
     def _kind(kind):
-        return _lib.KERNEL[kind] if kind in _lib.KERNEL else _lib.KERNEL_PER[kind]
+        for table in (_lib.KERNEL, _lib.KERNEL_PER, _lib.KERNEL_EVAL):
+            if kind in table:
+                return table[kind]
+        raise KeyError(kind)
 
     def prof_enable(self, kind, on=True):
         self._c("mdp_prof_enable", self._kind(kind), 1 if on else 0)

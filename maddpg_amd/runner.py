@@ -167,6 +167,11 @@ class VecRunner:
         """[count, 1 + n]: total reward (sum over agents) then per-agent rewards."""
         return self.eng.episode_log(first, count)
 
+    def evaluate(self, episodes, first_episode=0, mode="sample", bench=False):
+        """score the current policies on evaluation episodes (Engine.evaluate):
+        training's env copies, replay, log and counters are left alone"""
+        return self.eng.evaluate(episodes, first_episode=first_episode, mode=mode, bench=bench)
+
     def stats(self, agent):
         return self.eng.stats(agent)
 

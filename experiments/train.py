@@ -8,7 +8,9 @@ reference cadence (one round per 100 transitions; with E=1 -- the default --
 this is exactly the reference loop).  Extra flags: ``--num-envs``, ``--seed``,
 ``--num-agents``/``--scenario-adversaries`` (scenario size), ``--train-every``,
 ``--evaluate`` / ``--eval-episodes`` / ``--eval-mode`` / ``--adv-load-dir``
-(device-side policy evaluation on fixed episode ids; it leaves training untouched).
+(device-side policy evaluation on fixed episode ids; it leaves training untouched),
+``--evaluate --tournament DIR [DIR ...]`` / ``--tournament-team`` (the cross-play
+table of several checkpoints in one launch).
 
 Episode accounting follows the reference exactly: ``len(episode_rewards)`` is
 the number of finished episodes + 1 (a new 0 entry is appended at every reset,
@@ -106,6 +108,13 @@ def parse_args(argv=None):
     parser.add_argument("--adv-load-dir", type=str, default="",
                         help="--evaluate: take the first --num-adversaries agents from this checkpoint and the rest "
                              "from --load-dir (cross-play)")
+    parser.add_argument("--tournament", type=str, nargs="+", default=[], metavar="DIR",
+                        help="--evaluate: the K x K cross-play table of these checkpoints (each as --load-dir takes "
+                             "it) in one launch: the row checkpoint supplies the agents of --tournament-team, the "
+                             "column checkpoint the rest")
+    parser.add_argument("--tournament-team", type=str, default="",
+                        help="--tournament: comma-separated agent indices the row checkpoint supplies "
+                             "(default: the first --num-adversaries agents)")
     return parser.parse_args(argv)
 
 
@@ -241,6 +250,80 @@ def evaluate(arglist, runner, exp_name, rank):
     return runner
 
 
+def tournament_flags(arglist):
+    """--tournament's flag combinations, refused before anything is built"""
+    if arglist.tournament and not arglist.evaluate:
+        raise SystemExit("--tournament needs --evaluate")
+    if arglist.tournament and arglist.adv_load_dir:
+        raise SystemExit("--tournament and --adv-load-dir exclude each other (the tournament's rows are the "
+                         "adversary checkpoints)")
+
+
+def tournament_team(arglist, n):
+    """the agents the row checkpoint supplies: --tournament-team, or the first
+    --num-adversaries agents; an empty or full team is no cross-play"""
+    tournament_flags(arglist)
+    if arglist.tournament_team:
+        try:
+            team = sorted({int(x) for x in arglist.tournament_team.split(",")})
+        except ValueError:
+            raise SystemExit("--tournament-team: comma-separated agent indices, got {!r}".format(arglist.tournament_team))
+    else:
+        team = list(range(min(n, arglist.num_adversaries)))
+    if any(not 0 <= a < n for a in team):
+        raise SystemExit("--tournament-team {}: agent out of range for {} agents".format(team, n))
+    if not team:
+        raise SystemExit("--tournament: the team is empty (give --tournament-team or --num-adversaries)")
+    if len(team) == n:
+        raise SystemExit("--tournament: the team holds every agent, the column checkpoint would supply none")
+    return team
+
+
+def tournament(arglist, runner, exp_name, rank):
+    """--evaluate --tournament DIR [DIR ...]: every checkpoint's team against every
+    checkpoint's other agents on evaluation episodes [0, M) in one
+    Engine.evaluate_matchups call.  Prints the K x K table of the team's and the
+    others' mean return (the mean over the side's agents) with standard errors;
+    pickles the table, the per-episode returns and the checkpoint names to
+    <benchmark-dir><exp-name>_tournament.pkl."""
+    eng, sp, n = runner.eng, runner.spec, runner.n
+    team = tournament_team(arglist, n)
+    others = [j for j in range(n) if j not in team]
+    names = list(arglist.tournament)
+    K = len(names)
+    M = arglist.eval_episodes if arglist.eval_episodes > 0 else 1024
+    bank = eng.actor_bank(K)
+    for k, d in enumerate(names):
+        eng.bank_write(bank, k, d)
+    res = eng.cross_play(bank, team, M, 0, mode=arglist.eval_mode)
+    ret = res["returns"].cpu().numpy()                     # [K, K, M, n]
+    mean, sem = np.empty((K, K, n)), np.empty((K, K, n))
+    side = np.empty((K, K, 2, 2))                          # [row, column, team / others, mean / standard error]
+    for a in range(K):
+        for b in range(K):
+            r64 = np.ascontiguousarray(ret[a, b], np.float64)
+            mean[a, b], sem[a, b] = r64.mean(0), r64.std(0) / np.sqrt(M)
+            for q, ags in enumerate((team, others)):
+                s = r64[:, ags].mean(1)
+                side[a, b, q] = s.mean(), s.std() / np.sqrt(M)
+    out = {"scenario": sp.name, "mode": arglist.eval_mode, "episodes": M, "first_episode": 0, "checkpoints": names,
+           "team": team, "table": res["table"], "returns": ret, "mean": mean, "sem": sem, "side": side}
+    if rank == 0:
+        print("tournament: rows supply agents {}, columns agents {}; {} episodes".format(team, others, M), flush=True)
+        for k, d in enumerate(names):
+            print("tournament checkpoint {}: {}".format(k, d), flush=True)
+        for a in range(K):
+            for b in range(K):
+                print("tournament [{}][{}]: team mean return {} +- {}, others {} +- {}".format(
+                    a, b, side[a, b, 0, 0], side[a, b, 0, 1], side[a, b, 1, 0], side[a, b, 1, 1]), flush=True)
+        file_name = arglist.benchmark_dir + exp_name + '_tournament.pkl'
+        os.makedirs(os.path.dirname(file_name) or ".", exist_ok=True)
+        with open(file_name, 'wb') as fp:
+            pickle.dump(out, fp)
+    runner.synchronize()
+    return runner
+
+
 def display(arglist, runner, exp_name, rank):
     """--display (train.py:150-154): the loaded policies act, nothing trains,
     every step is rendered.  Headless: env copy 0 is rasterised to
@@ -265,6 +348,7 @@ def train(arglist):
     from maddpg_amd.parallel import init_process_group_from_env
     from maddpg_amd.runner import VecRunner
 
+    tournament_flags(arglist)
     exp_name = arglist.exp_name if arglist.exp_name is not None else arglist.scenario
     world, rank, local = init_process_group_from_env()
     if torch.cuda.is_available():
@@ -305,6 +389,8 @@ def _train(arglist, runner, exp_name, world, rank):
     say = (lambda *a: print(*a, flush=True)) if rank == 0 else (lambda *a: None)
     say('Using good policy {} and adv policy {}'.format(arglist.good_policy, arglist.adv_policy))
 
+    if arglist.tournament:     # the checkpoints go into a bank; the handle's own parameters are never played
+        return tournament(arglist, runner, exp_name, rank)
     if arglist.load_dir == "":
         arglist.load_dir = arglist.save_dir
     if arglist.restore or arglist.benchmark or arglist.display or arglist.evaluate:   # train.py:92-96

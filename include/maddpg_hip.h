@@ -18,7 +18,8 @@
  *    buffer (mdp_dp_xgmi_open: hipExtMallocWithFlags, uncached, IPC-exported,
  *    [2 slots][world][params + probe] 64-bit words; freed by
  *    mdp_dp_xgmi_close / mdp_destroy); mdp_eval_initial_state stages its
- *    result through a temporary device buffer that it frees before returning.
+ *    result, and mdp_evaluate_matchups its table, through a temporary device
+ *    buffer that it frees before returning.
  *  - "_dev" pointers are device pointers on the handle's device; "_host"
  *    pointers are host memory.  Device-pointer calls are asynchronous on the
  *    handle's stream unless stated; host-pointer calls synchronise.  Every
@@ -389,6 +390,56 @@ int mdp_evaluate(mdp_handle* h, int64_t first_episode, int32_t episodes, int32_t
  * (host, synchronises; staged through a temporary device buffer freed before return) */
 int mdp_eval_initial_state(mdp_handle* h, int64_t first_episode, int32_t episodes,
                            float* pos_host, float* vel_host, int32_t* goal_host);
+
+/* ---- matchup evaluation: a bank of actor sets scored in one launch --------
+ * mdp_evaluate's episodes with the actors taken from a caller-owned bank on
+ * the device instead of the handle's parameters: the cross-play table of the
+ * MADDPG paper (run A's adversaries against run B's good agents, every A and
+ * B), every checkpoint of a run on the same start states, seeds against each
+ * other.  The handle's own parameters are neither read nor written, so the
+ * calls work in the middle of a training run.
+ *   set       mdp_actor_set_floats() floats laid out as the theta region: agent
+ *             j's actor tensor t at mdp_tensor(j, 0, t).offset.  Only the actor
+ *             spans are ever read; what lies between them is never read.  The
+ *             value (the set stride of a bank) is mdp_arena_bytes' param_floats
+ *             rounded up to a multiple of 4; -1 on an unusable handle
+ *   bank      [n_sets][mdp_actor_set_floats()] floats, 16-byte aligned
+ *   table     [matchups][n_agents] int32 on the host: table[m][j] is the set that
+ *             agent j's actor comes from in matchup m
+ *   episode   id g as mdp_evaluate defines it: the same reset stream, noise
+ *             stream, step, ret and bench definitions.  Neither the start state
+ *             nor the noise depends on m, so two matchups on the same ids are a
+ *             paired comparison on common random numbers
+ *   ret       [m][i][j], bench [m][i][j][MDP_BENCH_W]
+ *   u_dev     NULL or [episodes][max_episode_len][n_agents][5], shared by every matchup
+ * mdp_actor_set_write takes the logical layout and the count of
+ * mdp_set_params(agent, MDP_ACTOR, ...) and writes the agent's whole device
+ * block (pad entries exact zeros) into set_dev; it touches neither the arena
+ * nor the handle's state and synchronises.  mdp_actor_set_snapshot copies every
+ * agent's actor span of the handle's current parameters into set_dev, device
+ * to device on the handle's stream (refused while the stream captures).
+ * mdp_evaluate_matchups checks the whole table on the host, stages it through
+ * a temporary device buffer that is freed before return -- so the call
+ * SYNCHRONISES the handle's stream, unlike mdp_evaluate -- and plays every
+ * (matchup, id) in one launch (grid: 16-id tiles x matchups), timed as
+ * MDP_K_EVAL.  Like mdp_evaluate it touches nothing training uses, and it never
+ * writes the bank.
+ * Bounds: 1 <= n_sets <= 4096, 1 <= matchups <= 4096, episodes and the id range
+ * as mdp_evaluate, matchups * episodes <= 2^22.
+ * Refused with a message that names the entry point and the argument, before
+ * any launch: a handle without a device env, a bad mode, u_dev with
+ * MDP_EVAL_MEAN, a NULL table_host / ret_dev / bank_dev, a table entry outside
+ * [0, n_sets) (the message gives the matchup and the agent), a bound above, a
+ * bank_dev that is not 16-byte aligned, bench_dev where mdp_evaluate refuses
+ * it, a capturing stream, and every _dev pointer that is not device memory of
+ * the full size (bank n_sets * stride, ret matchups * episodes * n_agents, ...). */
+int64_t mdp_actor_set_floats(const mdp_handle* h);
+int mdp_actor_set_write(mdp_handle* h, float* set_dev, int32_t agent, const float* src_host, int64_t n);
+int mdp_actor_set_snapshot(mdp_handle* h, float* set_dev);
+int mdp_evaluate_matchups(mdp_handle* h, const float* bank_dev, int32_t n_sets,
+                          const int32_t* table_host, int32_t matchups,
+                          int64_t first_episode, int32_t episodes, int32_t mode,
+                          const float* u_dev, float* ret_dev, float* bench_dev);
 /* finished-episode log: total entries written so far, copy last `n` [n][1+n_agents] */
 int64_t mdp_episode_count(mdp_handle* h);
 int mdp_episode_log(mdp_handle* h, int64_t first, int64_t n, float* out_host);
@@ -471,7 +522,7 @@ enum mdp_kernel_kind {
     MDP_K_APPLY = 4, MDP_K_ROLLOUT = 5, MDP_K_REDUCE = 6, MDP_K_REDUCE_APPLY = 7,
     MDP_K_ALLREDUCE = 8,   /* the RCCL data-parallel all-reduces (not a kernel of this library) */
     MDP_K_PER_SYNC = 9, MDP_K_PER_SAMPLE = 10, MDP_K_PER_UPDATE = 11,   /* prioritized replay (mdp_per.hip) */
-    MDP_K_EVAL = 12,       /* k_eval_episodes (mdp_evaluate) */
+    MDP_K_EVAL = 12,       /* k_eval_episodes (mdp_evaluate, mdp_evaluate_matchups) */
     MDP_K_COUNT = 13
 };
 int mdp_prof_enable(mdp_handle* h, int32_t kind, int32_t on);

@@ -626,6 +626,23 @@ int64_t net_floats(const mdp_handle* h, int agent, int net) {
   return s;
 }
 
+// the device block of agent's net from its logical (TF variable) layout, pad
+// entries exact zeros (mdp_set_params, mdp_actor_set_write)
+std::vector<float> scatter_net(const mdp_handle* h, int agent, int net, const float* src) {
+  const NDesc& d = net ? h->L.topo.ag[agent].critic : h->L.topo.ag[agent].actor;
+  std::vector<float> buf(d.size, 0.f);  // padded entries stay zero
+  int64_t s = 0;
+  for (int t = 0; t < 6; ++t) {
+    int rows, cols;
+    logical_shape(h, agent, net, t, &rows, &cols);
+    for (int r = 0; r < rows; ++r, s += cols) {
+      const int dr = (net && t == 0) ? critic_w1_dev_row(h, agent, r) : r;
+      std::memcpy(buf.data() + (d.t[t].off - d.off) + (int64_t)dr * d.t[t].cols, src + s, 4 * (int64_t)cols);
+    }
+  }
+  return buf;
+}
+
 int launch_make_index(mdp_handle* h, int count, int32_t* out) {
   if (h->len <= 0) return fail(h, "make_index on an empty replay buffer (randint(0, -1))");
   ProfScope p(h, MDP_K_INDEX);
@@ -1696,16 +1713,7 @@ int mdp_set_params(mdp_handle* h, int32_t agent, int32_t which, const float* src
   const NDesc& d = net_of(h, agent, net);
   if (n != net_floats(h, agent, net)) return fail(h, "param count mismatch");
   h->started = true;
-  std::vector<float> buf(d.size, 0.f);  // padded entries stay zero
-  int64_t s = 0;
-  for (int t = 0; t < 6; ++t) {
-    int rows, cols;
-    logical_shape(h, agent, net, t, &rows, &cols);
-    for (int r = 0; r < rows; ++r, s += cols) {
-      const int dr = (net && t == 0) ? critic_w1_dev_row(h, agent, r) : r;
-      std::memcpy(buf.data() + (d.t[t].off - d.off) + (int64_t)dr * d.t[t].cols, src + s, 4 * (int64_t)cols);
-    }
-  }
+  const std::vector<float> buf = scatter_net(h, agent, net, src);
   float* dst = (float*)(h->arena + h->L.off[region]) + d.off;
   HIPCHK(h, hipMemcpyAsync(dst, buf.data(), 4 * buf.size(), hipMemcpyHostToDevice, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -2606,6 +2614,120 @@ int mdp_eval_initial_state(mdp_handle* h, int64_t first_episode, int32_t episode
   }
   (void)hipFree(tmp);
   if (e != hipSuccess) return fail(h, "mdp_eval_initial_state", e);
+  return 0;
+}
+
+// ---- matchup evaluation (k_eval_episodes<H, EvalMuArgs>): a caller-owned bank
+// of actor sets, each laid out as the theta region
+#define MDP_EVAL_MAX_SETS 4096
+#define MDP_EVAL_MAX_MATCHUPS 4096
+#define MDP_EVAL_MAX_MATCHUP_EPISODES ((int64_t)1 << 22)
+static int64_t actor_set_floats(const mdp_handle* h) { return (h->L.PT + 3) & ~(int64_t)3; }
+static bool stream_captures(mdp_handle* h) {
+  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+  const bool c = h->capturing || (hipStreamIsCapturing(h->stream, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone);
+  (void)hipGetLastError();
+  return c;
+}
+
+int64_t mdp_actor_set_floats(const mdp_handle* h) { return unusable(h) ? -1 : actor_set_floats(h); }
+
+int mdp_actor_set_write(mdp_handle* h, float* set_dev, int32_t agent, const float* src_host, int64_t n) {
+  MDP_NEED(h);
+  if (agent < 0 || agent >= h->cfg.n_agents) return fail(h, "mdp_actor_set_write: agent index out of range");
+  if (!src_host) return fail(h, "mdp_actor_set_write: src_host is null");
+  if (n != net_floats(h, agent, 0)) return fail(h, "mdp_actor_set_write: n: param count mismatch");
+  if (stream_captures(h)) return fail(h, "mdp_actor_set_write: the handle's stream is capturing a graph");
+  MDP_DEV(h, set_dev, 4 * actor_set_floats(h), "mdp_actor_set_write", false);
+  const NDesc& d = h->L.topo.ag[agent].actor;
+  const std::vector<float> buf = scatter_net(h, agent, 0, src_host);
+  HIPCHK(h, hipMemcpyAsync(set_dev + d.off, buf.data(), 4 * buf.size(), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  return 0;
+}
+
+int mdp_actor_set_snapshot(mdp_handle* h, float* set_dev) {
+  MDP_NEED(h);
+  if (stream_captures(h)) return fail(h, "mdp_actor_set_snapshot: the handle's stream is capturing a graph");
+  MDP_DEV(h, set_dev, 4 * actor_set_floats(h), "mdp_actor_set_snapshot", false);
+  for (int j = 0; j < h->cfg.n_agents; ++j) {
+    const NDesc& d = h->L.topo.ag[j].actor;
+    HIPCHK(h, hipMemcpyAsync(set_dev + d.off, h->theta + d.off, 4 * (size_t)d.size, hipMemcpyDeviceToDevice, h->stream));
+  }
+  return 0;
+}
+
+int mdp_evaluate_matchups(mdp_handle* h, const float* bank_dev, int32_t n_sets, const int32_t* table_host,
+                          int32_t matchups, int64_t first_episode, int32_t episodes, int32_t mode, const float* u_dev,
+                          float* ret_dev, float* bench_dev) {
+  MDP_NEED(h);
+  const char* fn = "mdp_evaluate_matchups";
+  if (h->cfg.scenario == MDP_SCN_NONE || h->cfg.num_envs <= 0)
+    return fail(h, "mdp_evaluate_matchups: the handle has no device env");
+  if (mode != MDP_EVAL_SAMPLE && mode != MDP_EVAL_MEAN)
+    return fail(h, "mdp_evaluate_matchups: mode must be MDP_EVAL_SAMPLE (0) or MDP_EVAL_MEAN (1)");
+  if (n_sets < 1 || n_sets > MDP_EVAL_MAX_SETS) return fail(h, "mdp_evaluate_matchups: 1 <= n_sets <= 4096");
+  if (matchups < 1 || matchups > MDP_EVAL_MAX_MATCHUPS) return fail(h, "mdp_evaluate_matchups: 1 <= matchups <= 4096");
+  if (eval_range_ok(h, fn, first_episode, episodes)) return -1;
+  if ((int64_t)matchups * episodes > MDP_EVAL_MAX_MATCHUP_EPISODES)
+    return fail(h, "mdp_evaluate_matchups: matchups * episodes <= 2^22");
+  if (u_dev && mode == MDP_EVAL_MEAN)
+    return fail(h, "mdp_evaluate_matchups: u_dev is given but MDP_EVAL_MEAN draws no noise");
+  if (!bank_dev) return fail(h, "mdp_evaluate_matchups: bank_dev is null");
+  if (!table_host) return fail(h, "mdp_evaluate_matchups: table_host is null");
+  if (!ret_dev) return fail(h, "mdp_evaluate_matchups: ret_dev is null");
+  if (((uintptr_t)bank_dev & 15) != 0) return fail(h, "mdp_evaluate_matchups: bank_dev must be 16-byte aligned");
+  const int n = h->cfg.n_agents;
+  for (int m = 0; m < matchups; ++m)
+    for (int j = 0; j < n; ++j) {
+      const int32_t v = table_host[(int64_t)m * n + j];
+      if (v < 0 || v >= n_sets) {
+        char b[200];
+        std::snprintf(b, sizeof(b), "mdp_evaluate_matchups: table_host[matchup %d][agent %d] = %d is outside [0, n_sets = %d)",
+                      m, j, (int)v, (int)n_sets);
+        return fail(h, b);
+      }
+    }
+  if (stream_captures(h))
+    return fail(h, "mdp_evaluate_matchups: the handle's stream is capturing a graph (evaluation is not captured)");
+  const int64_t stride = actor_set_floats(h);
+  const int64_t en = 4 * (int64_t)episodes * n;
+  MDP_DEV(h, bank_dev, 4 * (int64_t)n_sets * stride, fn, false);
+  MDP_DEV(h, u_dev, en * h->cfg.max_episode_len * MDP_ACT_DIM, fn, true);
+  MDP_DEV(h, ret_dev, (int64_t)matchups * en, fn, false);
+  MDP_DEV(h, bench_dev, (int64_t)matchups * en * MDP_BENCH_W, fn, true);
+  if (bench_dev)
+    if (const char* why = no_bench_reason(h->cfg.scenario))
+      return fail(h, (std::string("mdp_evaluate_matchups: bench_dev: ") + why).c_str());
+  const int lds = lds_eval_matchups_bytes(h->L.topo);
+  if (lds > MDP_LDS_BUDGET) return fail(h, "mdp_evaluate_matchups: the configuration leaves no LDS for the table row");
+  int32_t* table_dev = nullptr;
+  const size_t tbytes = 4 * (size_t)matchups * n;
+  HIPCHK(h, hipMalloc((void**)&table_dev, tbytes));
+  hipError_t e = hipMemcpyAsync(table_dev, table_host, tbytes, hipMemcpyHostToDevice, h->stream);
+  if (e == hipSuccess) {
+    EvalMuArgs a;
+    a.topo = h->L.topo;
+    a.env = h->L.env;
+    a.theta = nullptr;
+    a.seed = h->cfg.seed;
+    a.first = (uint32_t)first_episode;
+    a.episodes = episodes;
+    a.mode = mode;
+    a.u_in = u_dev;
+    a.ret = ret_dev;
+    a.bench = bench_dev;
+    a.bank = bank_dev;
+    a.table = table_dev;
+    a.set_stride = stride;
+    a.matchups = matchups;
+    ProfScope p(h, MDP_K_EVAL);
+    e = mdp_launch_eval_matchups(a, h->L.topo.H, lds, h->stream);
+  }
+  const hipError_t es = hipStreamSynchronize(h->stream);
+  (void)hipFree(table_dev);
+  if (e != hipSuccess) return fail(h, "mdp_evaluate_matchups: launch", e);
+  if (es != hipSuccess) return fail(h, "mdp_evaluate_matchups: hipStreamSynchronize", es);
   return 0;
 }
 

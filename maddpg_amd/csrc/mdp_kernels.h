@@ -340,6 +340,15 @@ struct EvalEpArgs {
   float* bench;        // [episodes][n][MDP_BENCH_W] record sums or null
 };
 
+// k_eval_episodes<H, EvalMuArgs>: EvalEpArgs' episodes for every row of a matchup
+// table; theta is unused (agent j of matchup m plays bank + table[m][j] * set_stride)
+struct EvalMuArgs : EvalEpArgs {
+  const float* bank;     // [n_sets][set_stride], each set laid out as the theta region
+  const int32_t* table;  // [matchups][n] set indices (device)
+  int64_t set_stride;    // floats per set (mdp_actor_set_floats)
+  int matchups;          // ret [matchups][episodes][n], bench [matchups][episodes][n][MDP_BENCH_W]
+};
+
 struct EvalArgs {
   const float* P;
   NDesc net;
@@ -405,6 +414,8 @@ inline int lds_rollout_bytes(const Topo& t) {
   return 4 * (mdp_r4(R * ldr) + 2 * mdp_r4(R * ldh) + mdp_r4(R * 8) + par + 2 * mdp_r4(R * 2 * MDP_MAX_ENT) +
               mdp_r4(R * 3 * MDP_MAX_ENT) + mdp_r4(R * MDP_MAX_AGENTS) + mdp_r4(R));
 }
+// k_eval_episodes<H, EvalMuArgs>: k_rollout's carve plus the matchup's table row
+inline int lds_eval_matchups_bytes(const Topo& t) { return lds_rollout_bytes(t) + 4 * mdp_r4(MDP_MAX_AGENTS); }
 inline int lds_eval_bytes(int in, int H) {
   const int R = 16, ldx = mdp_ld(in), ldh = H + 1;
   return 4 * (mdp_r4(R * ldx) + 2 * mdp_r4(R * ldh) + mdp_r4(R * 8));
@@ -441,6 +452,7 @@ hipError_t mdp_launch_actor_grad_r(const ActorArgs& a, int lds_bytes, hipStream_
 hipError_t mdp_launch_rollout(const RolloutArgs& a, int H, int lds_bytes, hipStream_t s);
 hipError_t mdp_launch_eval(const EvalArgs& a, int H, int lds_bytes, hipStream_t s);
 hipError_t mdp_launch_eval_episodes(const EvalEpArgs& a, int H, int lds_bytes, hipStream_t s);
+hipError_t mdp_launch_eval_matchups(const EvalMuArgs& a, int H, int lds_bytes, hipStream_t s);
 hipError_t mdp_launch_eval_reset(const EnvDesc& env, uint64_t seed, uint32_t first, int count, float* pos, float* vel,
                                  int32_t* goal, hipStream_t s);
 hipError_t mdp_launch_apply(const ApplyArgs& a, hipStream_t s);

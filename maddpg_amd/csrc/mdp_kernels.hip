@@ -11,6 +11,8 @@
 //                                        + replay append + episode reset), k_env_reset
 //   train.py:139-148 (--benchmark: the policies play, nothing trains) -> k_eval_episodes
 //                                        (whole episodes per workgroup, no replay / log / Ctl)
+#include <type_traits>
+
 #include "mdp_device.h"
 #include "mdp_kernels.h"
 #include "mdp_mt.h"
@@ -1127,8 +1129,16 @@ __global__ __launch_bounds__(MDP_NT) void k_rollout(RolloutArgs a) {
 // Global traffic: the weights in, ret / bench out (and injected uniforms in).
 // Episode id g = first + its index: reset stream 0x60000 (ctr 0, env g), noise
 // stream 0x70000 | agent (ctr = step, row g).
-template <int H>
-__global__ __launch_bounds__(MDP_NT) void k_eval_episodes(EvalEpArgs a) {
+//
+// Args = EvalMuArgs (MU, mdp_evaluate_matchups): the same episode for every row
+// of a matchup table.  Workgroup (tile, matchup m) = (blockIdx.x, blockIdx.y)
+// reads agent j's actor from bank + table[m][j] * set_stride in place of theta
+// and writes ret / bench at [m][episode][agent]; ids, reset and noise streams
+// and the injected uniforms do not depend on m.  Everything else is the code
+// below, unchanged; the EvalEpArgs instantiations compile to what they were.
+template <int H, class Args = EvalEpArgs>
+__global__ __launch_bounds__(MDP_NT) void k_eval_episodes(Args a) {
+  constexpr bool MU = std::is_same<Args, EvalMuArgs>::value;
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const Topo& T = a.topo;
   const EnvDesc& E = a.env;
@@ -1146,6 +1156,8 @@ __global__ __launch_bounds__(MDP_NT) void k_eval_episodes(EvalEpArgs a) {
   float* sfo = cv.take(MDP_R * 3 * MDP_MAX_ENT);
   float* epr = cv.take(MDP_R * MDP_MAX_AGENTS);  // the episodes' returns so far
   int* sgoal = reinterpret_cast<int*>(cv.take(MDP_R));
+  // MU: the matchup's table row (lds_eval_matchups_bytes adds it behind k_rollout's carve)
+  int* stab = MU ? reinterpret_cast<int*>(cv.take(MDP_MAX_AGENTS)) : nullptr;
   // this step's records of the tile, [R][n][MDP_BENCH_W]: in h1, which is free
   // between a step's forward and the next one's
   static_assert(MDP_R * MDP_MAX_AGENTS * MDP_BENCH_W <= MDP_R * (H + 1), "record tile fits h1");
@@ -1161,6 +1173,9 @@ __global__ __launch_bounds__(MDP_NT) void k_eval_episodes(EvalEpArgs a) {
   for (int q = tid; q < MDP_R * 2 * MDP_MAX_ENT; q += MDP_NT) sp[q] = sv[q] = 0.f;
   if (tid < MDP_R * MDP_MAX_AGENTS) epr[tid] = 0.f;
   if (tid < MDP_R) sgoal[tid] = 0;
+  if constexpr (MU) {
+    if (tid < n) stab[tid] = a.table[(int64_t)blockIdx.y * n + tid];
+  }
   __syncthreads();
   if (tid < nvalid) {
     int32_t g;
@@ -1184,6 +1199,7 @@ __global__ __launch_bounds__(MDP_NT) void k_eval_episodes(EvalEpArgs a) {
       const ADesc& aj = T.ag[wave];
       const NDesc& an = aj.actor;
       const float* P = a.theta;
+      if constexpr (MU) P = a.bank + (int64_t)a.table[(int64_t)blockIdx.y * n + wave] * a.set_stride;
       rf_load<16>(w1, P + an.t[0].off, aj.obs_dim);
       rf_load<16>(w2, P + an.t[2].off, MDP_RH);
       rh_load(w3, P + an.t[4].off, MDP_ACT_DIM);
@@ -1267,14 +1283,16 @@ __global__ __launch_bounds__(MDP_NT) void k_eval_episodes(EvalEpArgs a) {
     }
     for (int j = 0; j < (par ? 0 : n); ++j) {
       const ADesc& aj = T.ag[j];
+      const float* Pj = a.theta;
+      if constexpr (MU) Pj = a.bank + (int64_t)stab[j] * a.set_stride;
       bool pf = false;
       if constexpr (H == 64 && MDP_NW == 4) {
         if (aj.obs_dim <= 4 * MDP_KC) {
-          mlp_fwd_tile_pf<H>(rowt + aj.obs_off, ldr, aj.obs_dim, a.theta, aj.actor, h1, h2, ldh, lg, 8);
+          mlp_fwd_tile_pf<H>(rowt + aj.obs_off, ldr, aj.obs_dim, Pj, aj.actor, h1, h2, ldh, lg, 8);
           pf = true;
         }
       }
-      if (!pf) mlp_fwd_tile<H>(rowt + aj.obs_off, ldr, aj.obs_dim, a.theta, aj.actor, h1, h2, ldh, lg, 8);
+      if (!pf) mlp_fwd_tile<H>(rowt + aj.obs_off, ldr, aj.obs_dim, Pj, aj.actor, h1, h2, ldh, lg, 8);
       if (tid < MDP_R) sample(lg + tid * 8, tid, j, rowt + tid * ldr + aj.act_off);
       __syncthreads();
     }
@@ -1298,7 +1316,8 @@ __global__ __launch_bounds__(MDP_NT) void k_eval_episodes(EvalEpArgs a) {
   }
 
   if (tid < MDP_R * n && br < nvalid) {
-    const int64_t o = (int64_t)(i0 + br) * n + bj;
+    int64_t o = (int64_t)(i0 + br) * n + bj;
+    if constexpr (MU) o += (int64_t)blockIdx.y * a.episodes * n;
     a.ret[o] = epr[br * MDP_MAX_AGENTS + bj];
     if (a.bench) {
 #pragma unroll
@@ -1391,6 +1410,8 @@ static void raise_lds_limits() {
   (void)hipFuncSetAttribute((const void*)k_rollout<H, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
   (void)hipFuncSetAttribute((const void*)k_mlp_eval<H>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
   (void)hipFuncSetAttribute((const void*)k_eval_episodes<H>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
+  (void)hipFuncSetAttribute((const void*)k_eval_episodes<H, EvalMuArgs>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                            128 * 1024);
 }
 static void ensure_lds_limits() {
   if (!set_lds_limit_done) {
@@ -1432,6 +1453,24 @@ hipError_t mdp_launch_eval_episodes(const EvalEpArgs& a, int H, int lds_bytes, h
     case 64: return launch_eval_episodes_t<64>(a, lds_bytes, s);
     case 128: return launch_eval_episodes_t<128>(a, lds_bytes, s);
     case 256: return launch_eval_episodes_t<256>(a, lds_bytes, s);
+    default: return hipErrorInvalidValue;
+  }
+}
+// grid: tile fastest, matchup second -- the workgroups of one matchup are
+// adjacent and share its weights in L2
+template <int H>
+static hipError_t launch_eval_matchups_t(const EvalMuArgs& a, int lds_bytes, hipStream_t s) {
+  const dim3 grid((a.episodes + MDP_R - 1) / MDP_R, a.matchups);
+  mdp_launch(k_eval_episodes<H, EvalMuArgs>, grid, dim3(MDP_NT), lds_bytes, s, a);
+  MDP_CHECK_LAUNCH();
+  return hipSuccess;
+}
+hipError_t mdp_launch_eval_matchups(const EvalMuArgs& a, int H, int lds_bytes, hipStream_t s) {
+  ensure_lds_limits();
+  switch (H) {
+    case 64: return launch_eval_matchups_t<64>(a, lds_bytes, s);
+    case 128: return launch_eval_matchups_t<128>(a, lds_bytes, s);
+    case 256: return launch_eval_matchups_t<256>(a, lds_bytes, s);
     default: return hipErrorInvalidValue;
   }
 }

@@ -30,6 +30,32 @@ def update_stats(vals):
     return [dt(v) for dt, v in zip(UPDATE_STAT_DTYPES, list(vals))]
 
 
+def read_checkpoint(fname, path, n, sets):
+    """(state_dict()-style dict, the path that was read) of a checkpoint of `n`
+    agents' parameter sets `sets` (Engine.load_state, Engine.bank_write).
+    Read from a TF1 tensor bundle at prefix `fname` (the reference's
+    tf.train.Saver checkpoint, tf_util.py:259-264) or from the .npz `path`
+    that save_state writes.  save_state removes the other format's files, so
+    both exist only when another tool wrote one of them: then the newer
+    one (nanosecond modification times) is read; on a tie (a copy that
+    kept timestamps, a tar archive's whole-second times) the TF1 bundle,
+    the reference's own format, is read and a warning names the choice."""
+    from .common import tf_checkpoint as tfc
+    if tfc.is_bundle(fname) and os.path.isfile(path):
+        t_npz, t_tf1 = os.stat(path).st_mtime_ns, os.stat(fname + ".index").st_mtime_ns
+        if t_npz == t_tf1:
+            import warnings
+            warnings.warn(f"both {path} and the TF1 bundle {fname}.index exist with the same modification "
+                          f"time; restoring the TF1 bundle (remove it to restore the .npz)")
+        use_tf1 = t_tf1 >= t_npz
+    else:
+        use_tf1 = tfc.is_bundle(fname)
+    if use_tf1:
+        return tfc.state_from_tf1(tfc.read_bundle(fname), n, sets), fname
+    with np.load(path, allow_pickle=False) as z:
+        return {k: z[k] for k in z.files}, path
+
+
 class Engine:
     def __init__(self, obs_dims, local_q=None, *, num_units=64, batch_size=1024, max_episode_len=25,
                  capacity=int(1e6), num_envs=0, scenario="none", num_adversaries=0, lr=1e-2,
@@ -234,14 +260,19 @@ class Engine:
         net = 1 if "critic" in which else 0
         return [(r, c) for (_o, r, c, _dr, _dc) in self._tensors[(agent, net)]]
 
-    def set_params(self, agent, which, params):
+    def _flat_params(self, agent, which, params):
+        """the logical layout mdp_set_params / mdp_actor_set_write take: a dict of
+        the six tensors (reshaped to their logical shapes) or a flat array"""
         shapes = self._flat_shapes(agent, which)
         if isinstance(params, dict):
             parts = [np.asarray(params[k], np.float32).reshape(s) for k, s in zip(TENSOR_NAMES, shapes)]
             flat = np.concatenate([p.ravel() for p in parts])
         else:
             flat = np.asarray(params, np.float32).ravel()
-        flat = np.ascontiguousarray(flat, np.float32)
+        return np.ascontiguousarray(flat, np.float32)
+
+    def set_params(self, agent, which, params):
+        flat = self._flat_params(agent, which, params)
         self._c("mdp_set_params", agent, _lib.WHICH[which], _lib.fptr(flat), flat.size)
 
     def get_params(self, agent, which):
@@ -353,32 +384,12 @@ class Engine:
 
     def load_state(self, fname, agents=None):
         """agents: a list restores only those agents' parameter sets (cross-play of
-        two checkpoints); None restores every agent.
-        Restore from a TF1 tensor bundle at prefix `fname` (the reference's
-        tf.train.Saver checkpoint, tf_util.py:259-264) or from the .npz
-        save_state writes.  save_state removes the other format's files, so
-        both exist only when another tool wrote one of them: then the newer
-        one (nanosecond modification times) is read; on a tie (a copy that
-        kept timestamps, a tar archive's whole-second times) the TF1 bundle,
-        the reference's own format, is read and a warning names the choice."""
-        from .common import tf_checkpoint as tfc
-        path = self.checkpoint_path(fname)
-        if tfc.is_bundle(fname) and os.path.isfile(path):
-            t_npz, t_tf1 = os.stat(path).st_mtime_ns, os.stat(fname + ".index").st_mtime_ns
-            if t_npz == t_tf1:
-                import warnings
-                warnings.warn(f"both {path} and the TF1 bundle {fname}.index exist with the same modification "
-                              f"time; restoring the TF1 bundle (remove it to restore the .npz)")
-            use_tf1 = t_tf1 >= t_npz
-        else:
-            use_tf1 = tfc.is_bundle(fname)
+        two checkpoints); None restores every agent.  The checkpoint is read as
+        read_checkpoint reads it."""
+        sd, used = read_checkpoint(fname, self.checkpoint_path(fname), self.n, self.SETS)
         more = () if agents is None else (agents,)
-        if use_tf1:
-            self.load_state_dict(tfc.state_from_tf1(tfc.read_bundle(fname), self.n, self.SETS), *more)
-            return fname
-        with np.load(path, allow_pickle=False) as z:
-            self.load_state_dict({k: z[k] for k in z.files}, *more)
-        return path
+        self.load_state_dict(sd, *more)
+        return used
 
     # ------------------------------------------------------------- replay
     def buffer_len(self):
@@ -878,6 +889,128 @@ class Engine:
         self._c("mdp_eval_initial_state", int(first_episode), episodes, _lib.fptr(pos), _lib.fptr(vel),
                 goal.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)))
         return {"pos": pos, "vel": vel, "goal": goal}
+
+    # ------------------------------------------------- matchup evaluation
+    def actor_set_floats(self):
+        """floats of one actor set, the stride of a bank (mdp_actor_set_floats)"""
+        v = int(self.lib.mdp_actor_set_floats(self.h))
+        if v < 0:
+            raise _lib.MdpError("mdp_actor_set_floats: unusable handle")
+        return v
+
+    def actor_bank(self, n_sets):
+        """a zero-filled bank of `n_sets` actor sets: float32 device tensor
+        [n_sets, set_floats], each set laid out as the theta region (agent j's
+        actor tensor t at mdp_tensor(j, 0, t).offset)"""
+        n_sets = int(n_sets)
+        if not 1 <= n_sets <= _lib.EVAL_MAX_SETS:
+            raise ValueError(f"actor_bank: 1 <= n_sets <= {_lib.EVAL_MAX_SETS}, got {n_sets}")
+        return torch.zeros((n_sets, self.actor_set_floats()), dtype=torch.float32, device=self.device)
+
+    def _bank_slot(self, bank, k):
+        sf = self.actor_set_floats()
+        if (not isinstance(bank, torch.Tensor) or bank.dtype != torch.float32 or bank.device != self.device
+                or not bank.is_contiguous()):
+            raise ValueError("bank: a contiguous float32 tensor on the engine's device (actor_bank)")
+        if bank.numel() == 0 or bank.numel() % sf:
+            raise ValueError(f"bank: {bank.numel()} elements, a set has {sf}")
+        k = int(k)
+        if not 0 <= k < bank.numel() // sf:
+            raise ValueError(f"bank slot {k} out of range for {bank.numel() // sf} sets")
+        return bank.view(-1, sf)[k]
+
+    def bank_snapshot(self, bank, k):
+        """copy the handle's current actors into slot k of the bank (mdp_actor_set_snapshot)"""
+        slot = self._bank_slot(bank, k)
+        self.sync_in()
+        self._c("mdp_actor_set_snapshot", self._ptr(slot))
+        self.sync_out()
+
+    def bank_write(self, bank, k, source, agents=None):
+        """write actors into slot k of the bank: `source` is a state_dict()-style
+        dict or a checkpoint path (npz or TF1 bundle, read as load_state reads
+        it); agents: only these agents' actors (None: every agent).  The
+        handle's own parameters are not touched (mdp_actor_set_write)."""
+        slot = self._bank_slot(bank, k)
+        sd = source
+        if not isinstance(source, dict):
+            sd = read_checkpoint(source, self.checkpoint_path(source), self.n, self.SETS)[0]
+        todo = range(self.n) if agents is None else sorted({int(a) for a in agents})
+        flats = []
+        for i in todo:
+            if not 0 <= i < self.n:
+                raise ValueError(f"agent {i} out of range for {self.n} agents")
+            flats.append((i, self._flat_params(i, "actor", {t: sd[f"agent_{i}/actor/{t}"] for t in TENSOR_NAMES})))
+        self.sync_in()
+        for i, flat in flats:
+            self._c("mdp_actor_set_write", self._ptr(slot), i, _lib.fptr(flat), flat.size)
+        self.sync_out()
+
+    def evaluate_matchups(self, bank, table, episodes, first_episode=0, mode="sample", bench=False, u=None):
+        """Score every row of a matchup table on evaluation episodes
+        [first_episode, first_episode + episodes) in one launch
+        (mdp_evaluate_matchups).  table [M, n] int32: table[m][j] is the set of
+        `bank` that agent j's actor comes from.  Episodes are mdp_evaluate's:
+        start state and noise depend on the id alone, so matchups on the same
+        ids are paired on common random numbers.  The handle's parameters are
+        neither read nor written.  u: [episodes, max_episode_len, n, 5]
+        injected uniforms shared by every matchup (sample mode).  Returns a
+        dict: `returns` [M, episodes, n] float32 device tensor, `bench`
+        [M, episodes, n, BENCH_W] or None, `summary` per-matchup, per-agent
+        mean / population std / standard error of the returns in fp64."""
+        if mode not in _lib.EVAL_MODE:
+            raise ValueError(f"unknown evaluation mode {mode!r} (sample, mean)")
+        episodes, first_episode = int(episodes), int(first_episode)
+        sf = self.actor_set_floats()
+        if (not isinstance(bank, torch.Tensor) or bank.dtype != torch.float32 or bank.device != self.device
+                or not bank.is_contiguous()):
+            raise ValueError("bank: a contiguous float32 tensor on the engine's device (actor_bank)")
+        n_sets = bank.numel() // sf
+        self._sized("bank", bank, max(n_sets, 1) * sf)
+        tab = table.cpu().numpy() if isinstance(table, torch.Tensor) else np.asarray(table)
+        if tab.dtype != np.int32:
+            raise ValueError(f"table: dtype {tab.dtype}, the call reads int32")
+        if tab.ndim != 2 or tab.shape[1] != self.n or tab.shape[0] < 1:
+            raise ValueError(f"table: shape {tab.shape}, expected [matchups, {self.n}]")
+        tab = np.ascontiguousarray(tab)
+        M = tab.shape[0]
+        uu = None if u is None else u.to(self.device, torch.float32).contiguous()
+        self._sized("u", uu, episodes * self.max_episode_len * self.n * _lib.ACT_DIM)
+        ne = max(episodes, 0)
+        ret = torch.empty((M, ne, self.n), dtype=torch.float32, device=self.device)
+        rec = None
+        if bench:
+            rec = torch.empty((M, ne, self.n, _lib.BENCH_W), dtype=torch.float32, device=self.device)
+        self.sync_in()
+        self._c("mdp_evaluate_matchups", self._ptr(bank), n_sets, tab.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
+                M, first_episode, episodes, _lib.EVAL_MODE[mode], self._ptr(uu), self._ptr(ret), self._ptr(rec))
+        self.sync_out()
+        r64 = ret.double()
+        std = r64.std(1, unbiased=False)
+        summary = {"mean": r64.mean(1).tolist(), "std": std.tolist(), "sem": (std / ne ** 0.5).tolist()}
+        return {"returns": ret, "bench": rec, "summary": summary}
+
+    def cross_play(self, bank, team, episodes, first_episode=0, mode="sample", bench=False, u=None):
+        """The K x K cross-play table of a bank of K sets: in cell (a, b) the agents
+        in `team` play set a's actors and the others set b's.  One
+        evaluate_matchups call (table construction only).  Returns a dict:
+        `mean` / `sem` [K, K, n] float64 numpy arrays (per-agent mean return and
+        its standard error), `table` [K * K, n], `returns` [K, K, episodes, n]
+        and `bench` [K, K, episodes, n, BENCH_W] or None."""
+        K = bank.numel() // self.actor_set_floats()
+        team = sorted({int(a) for a in team})
+        if any(not 0 <= a < self.n for a in team):
+            raise ValueError(f"team {team}: agents out of range for {self.n} agents")
+        table = np.empty((K, K, self.n), np.int32)
+        for j in range(self.n):
+            table[:, :, j] = np.arange(K)[:, None] if j in team else np.arange(K)[None, :]
+        table = table.reshape(K * K, self.n)
+        r = self.evaluate_matchups(bank, table, episodes, first_episode, mode, bench, u)
+        shape = (K, K, self.n)
+        return {"mean": np.asarray(r["summary"]["mean"], np.float64).reshape(shape),
+                "sem": np.asarray(r["summary"]["sem"], np.float64).reshape(shape), "table": table,
+                "returns": r["returns"].view(K, K, -1, self.n),
+                "bench": None if r["bench"] is None else r["bench"].view(K, K, -1, self.n, _lib.BENCH_W)}
 
     def env_state(self):
         E, ne = self.num_envs, self.n_entities

@@ -95,6 +95,12 @@ def parse_args(argv=None):
     parser.add_argument("--per-beta0", type=float, default=0.4, help="initial importance-sampling exponent (:150)")
     parser.add_argument("--per-beta-inc", type=float, default=0.001, help="beta increment per sample call (:151)")
     parser.add_argument("--per-eps", type=float, default=0.01, help="added to |TD error| before the clip (:148)")
+    parser.add_argument("--td3", action="store_true", default=False,
+                        help="MATD3: twin critics per agent, the TD target from the smaller target critic, the "
+                             "policy and the target nets updated every --policy-delay-th critic step (strict "
+                             "mode, one GPU, npz checkpoints; not with --prioritized-replay)")
+    parser.add_argument("--policy-delay", type=int, default=2,
+                        help="--td3: critic steps per policy / target update, 1..8 (1: twin critics without delay)")
     # device-side policy evaluation (whole episodes in one launch; training state untouched)
     parser.add_argument("--evaluate", action="store_true", default=False,
                         help="load as --benchmark does and score the policies on evaluation episodes 0 .. "
@@ -356,16 +362,35 @@ def train(arglist):
     from maddpg_amd._lib import MdpError
     from maddpg_amd.common.tf_util import per_kwargs
     per = per_kwargs(arglist)
+    td3_flags(arglist, world)
     try:
         runner = _make_runner(arglist, VecRunner, world, rank, per)
     except MdpError as e:      # e.g. prioritized replay with throughput mode or several GPUs
-        if not per:
+        if not per and not arglist.td3:
             raise
         raise SystemExit(str(e))
     return _train(arglist, runner, exp_name, world, rank)
 
 
+def td3_flags(arglist, world=1):
+    """--td3 is MATD3 on one GPU in strict mode with npz checkpoints: refuse the
+    combinations the library has no variant for before anything is built"""
+    if not getattr(arglist, "td3", False):
+        return
+    if not 1 <= arglist.policy_delay <= 8:
+        raise SystemExit("--policy-delay must be in 1..8")
+    if arglist.prioritized_replay:
+        raise SystemExit("--td3 does not combine with --prioritized-replay")
+    if arglist.update_mode != "strict":
+        raise SystemExit("--td3 needs --update-mode strict")
+    if (arglist.num_gpus or 1) > 1 or world > 1:
+        raise SystemExit("--td3 runs on one GPU (--num-gpus 1)")
+    if arglist.save_format == "tf1":
+        raise SystemExit("--td3 saves npz checkpoints only (the second critic has no reference variable names)")
+
+
 def _make_runner(arglist, VecRunner, world, rank, per):
+    from maddpg_amd.common.tf_util import td3_kwargs
     runner = VecRunner(arglist.scenario, arglist.num_envs, n_agents=arglist.num_agents,
                        scenario_adversaries=arglist.scenario_adversaries,
                        num_adversaries=arglist.num_adversaries, good_policy=arglist.good_policy,
@@ -377,7 +402,7 @@ def _make_runner(arglist, VecRunner, world, rank, per):
                        capacity=arglist.buffer_size,
                        # the learning-curve windows of one terminal step span <= save_rate + E episodes
                        episode_log_rows=max(4096, 4 * arglist.num_envs, arglist.save_rate + 2 * arglist.num_envs),
-                       **per)
+                       **per, **td3_kwargs(arglist))
     if arglist.update_mode != "strict":
         runner.eng.set_update_mode(arglist.update_mode)
     return runner
@@ -474,6 +499,7 @@ def _train(arglist, runner, exp_name, world, rank):
 def main(argv=None):
     argv = sys.argv[1:] if argv is None else list(argv)
     arglist = parse_args(argv)
+    td3_flags(arglist)
     if arglist.num_gpus is not None:
         from maddpg_amd.launch import rank_launch_plan, run_ranks
         plan = rank_launch_plan(arglist.num_gpus, os.environ, os.path.abspath(__file__), argv,

@@ -64,7 +64,9 @@ enum mdp_scenario {
 enum mdp_which {
     MDP_ACTOR = 0, MDP_CRITIC = 1, MDP_TGT_ACTOR = 2, MDP_TGT_CRITIC = 3,
     MDP_M_ACTOR = 4, MDP_V_ACTOR = 5, MDP_M_CRITIC = 6, MDP_V_CRITIC = 7,
-    MDP_G_ACTOR = 8, MDP_G_CRITIC = 9
+    MDP_G_ACTOR = 8, MDP_G_CRITIC = 9,
+    /* MATD3 (mdp_td3_enable): the second critic's sets, in the TD3 buffer; shapes and pad rules are the critic's */
+    MDP_CRITIC2 = 10, MDP_TGT_CRITIC2 = 11, MDP_M_CRITIC2 = 12, MDP_V_CRITIC2 = 13, MDP_G_CRITIC2 = 14
 };
 
 /* arena regions (mdp_region) */
@@ -515,6 +517,37 @@ int mdp_per_get_tree(mdp_handle* h, int32_t agent, float* nodes_host);
 /* out5 = {beta, total (root.sum), p_min (root.min), ring rows synced into the
  * trees so far, sample calls of this agent}; synchronises */
 int mdp_per_info(mdp_handle* h, int32_t agent, double out5[5]);
+
+/* ---- MATD3: twin critics, clipped double-Q target, delayed policy updates --
+ * (DESIGN.md section 17).  Every agent gets a second critic Q2 with its own target,
+ * Adam slots and beta powers in a SECOND caller-allocated device buffer of
+ * mdp_td3_bytes(cfg) bytes, which must outlive the handle.  Agent i's k-th
+ * update since enable (k = 1, 2, ...):
+ *   y = r + gamma (1 - done) min(Q1_tgt(x'), Q2_tgt(x'))   (fp32 min, fp64 TD line)
+ *   both critics step on mean (Q_c(x) - y)^2 with their own Adam;
+ *   if k % policy_delay == 0: the actor step (on Q1 after its step), then
+ *   Polyak of the target actor, target Q1 and target Q2; otherwise the actor,
+ *   its Adam state and all three targets stay bit-unchanged.
+ * The training-noise counter advances once per agent update either way.
+ * mdp_get_stats: [0] critic 1's loss, [1] p_loss of the most recent actor step
+ * (0 before the first), [4] the mean of min(q1', q2'), the rest as without TD3.
+ * policy_delay in 1..8 (1: twin critics without delay).  Enable comes before
+ * the handle's first update / train call.  MATD3 runs in strict mode on one
+ * GPU on the general gradient kernels; refused: prioritized replay, throughput
+ * mode, mdp_update_all, data parallelism, and the phase entry points
+ * mdp_critic_grad / mdp_actor_grad / mdp_reduce_grad / mdp_apply_grad.
+ * mdp_set_params / mdp_get_params take MDP_CRITIC2 .. MDP_G_CRITIC2 and
+ * mdp_get_beta_powers / mdp_set_beta_powers net = 2 on a TD3 handle only.
+ * The per-agent update counters live on the host and start at 0 at enable.
+ * The buffer starts with the second critic's five param-space regions (theta,
+ * target, Adam m, Adam v, reduced gradient: param_floats floats each, every
+ * region rounded up to 256 bytes, tensors at the arena regions' offsets; the
+ * actor spans stay zero); its partials, stats and sync area follow. */
+int64_t mdp_td3_bytes(const mdp_config* cfg);
+int mdp_td3_enable(mdp_handle* h, void* buf_dev, int64_t bytes, int32_t policy_delay);
+/* out4 = {critic updates, actor updates, q_loss of critic 1, q_loss of critic 2}
+ * of agent's last update; synchronises */
+int mdp_td3_info(mdp_handle* h, int32_t agent, double out4[4]);
 
 /* ---- profiling: HIP events bracketing every launch of one kernel kind -- */
 enum mdp_kernel_kind {

@@ -27,7 +27,9 @@ ABI_VERSION = 5
 SCN = {"none": 0, "simple": 1, "simple_spread": 2, "simple_adversary": 3, "simple_tag": 4,
        "simple_speaker_listener": 5}
 WHICH = {"actor": 0, "critic": 1, "tgt_actor": 2, "tgt_critic": 3, "m_actor": 4, "v_actor": 5,
-         "m_critic": 6, "v_critic": 7, "g_actor": 8, "g_critic": 9}
+         "m_critic": 6, "v_critic": 7, "g_actor": 8, "g_critic": 9,
+         # MATD3 (mdp_td3_enable): the second critic's sets
+         "critic2": 10, "tgt_critic2": 11, "m_critic2": 12, "v_critic2": 13, "g_critic2": 14}
 REGION = {"theta": 0, "target": 1, "adam_m": 2, "adam_v": 3, "grad": 4, "replay": 5, "index": 6,
           "stats": 7, "env": 8, "eplog": 9, "beta": 10, "slab": 11, "ctl": 12}
 KERNEL = {"index": 0, "gather": 1, "critic_grad": 2, "actor_grad": 3, "apply": 4, "rollout": 5,
@@ -170,6 +172,9 @@ SIGNATURES = {
     "mdp_per_tree_nodes": (_I64, [_P]),
     "mdp_per_get_tree": (ctypes.c_int, [_P, _I32, _F32P]),
     "mdp_per_info": (ctypes.c_int, [_P, _I32, _F64P]),
+    "mdp_td3_bytes": (_I64, [ctypes.POINTER(MdpConfig)]),
+    "mdp_td3_enable": (ctypes.c_int, [_P, _P, _I64, _I32]),
+    "mdp_td3_info": (ctypes.c_int, [_P, _I32, _F64P]),
     "mdp_prof_enable": (ctypes.c_int, [_P, _I32, _I32]),
     "mdp_prof_read": (ctypes.c_int, [_P, _I32, _F64P, ctypes.POINTER(_I64)]),
 }

@@ -70,7 +70,7 @@ class Session:
         seed = self.seed if self.seed is not None else int(getattr(args, "seed", 0) or 0)
         self._engine = Engine(obs_dims, local_q, num_units=args.num_units, batch_size=args.batch_size,
                               max_episode_len=args.max_episode_len, capacity=int(1e6), lr=args.lr,
-                              gamma=args.gamma, seed=seed, act_dims=t0.act_dims, **per_kwargs(args))
+                              gamma=args.gamma, seed=seed, act_dims=t0.act_dims, **per_kwargs(args), **td3_kwargs(args))
         self._engine.init_params(seed)
         return self._engine
 
@@ -147,6 +147,13 @@ def sync_rng_from_device(engine, st):
     """Write the device MT19937 state back into the module-global RNG."""
     new = engine.get_rng_state()
     random.setstate((st[0], tuple(int(x) for x in new), st[2]))
+
+
+def td3_kwargs(args):
+    """Engine keywords of --td3 / --policy-delay (experiments/train.py); {} when off"""
+    if not getattr(args, "td3", False):
+        return {}
+    return dict(td3=True, policy_delay=getattr(args, "policy_delay", 2))
 
 
 def per_kwargs(args):

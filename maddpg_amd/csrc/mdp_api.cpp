@@ -15,6 +15,7 @@
 #include <dlfcn.h>
 #include <rccl/rccl.h>
 
+#include <functional>
 #include <map>
 #include <vector>
 
@@ -406,6 +407,22 @@ struct mdp_handle {
   int64_t per_P = 0;
   float per_alpha = 0.6f, per_beta0 = 0.4f, per_beta_inc = 0.001f, per_eps = 0.01f, per_upper = 1.0f;
   int64_t per_host_total = 0;         // mdp_buffer_set_ring's rows_total at the last call
+  // MATD3 (mdp_td3_enable): the caller's TD3 buffer -- the second critic's five
+  // param-space regions (the arena's offsets; actor spans unused), its partials
+  // and records, beta powers, stats and its optimizer's own sync area
+  bool td3 = false;
+  int td3_delay = 2;
+  float *theta2 = nullptr, *target2 = nullptr, *m2 = nullptr, *v2 = nullptr, *grad2 = nullptr;
+  float *slab2 = nullptr, *beta2 = nullptr;
+  double *stat2 = nullptr, *stats2 = nullptr;
+  uint32_t *ra_ctr2 = nullptr, *ticket2 = nullptr;
+  uint64_t* ra_part2 = nullptr;
+  // updates of agent i since enable: committed once the launch or replay was
+  // issued (td3_count), and as the launches being issued or captured see it (td3_work)
+  int64_t td3_count[MDP_MAX_AGENTS] = {};
+  int64_t td3_work[MDP_MAX_AGENTS] = {};
+  // graphs keyed by {kind (0 round, 1 step, 2 group), every agent's count mod d, the round counts}
+  std::map<std::vector<int>, hipGraphExec_t> td3_exec;
 };
 
 namespace {
@@ -572,6 +589,27 @@ int region_for(int which, int* region, int* net) {
     case MDP_G_CRITIC: *region = MDP_R_GRAD; *net = 1; return 0;
     default: return -1;
   }
+}
+
+// base of the param-space region that holds parameter set `which` -- the
+// arena's, or the TD3 buffer's for the second critic's sets -- and its net;
+// null with the reason in the handle's error
+float* which_base(mdp_handle* h, int which, int* net) {
+  if (which >= MDP_CRITIC2 && which <= MDP_G_CRITIC2) {
+    if (!h->td3) {
+      fail(h, "which: the second critic's sets (10..14) need MATD3 (mdp_td3_enable)");
+      return nullptr;
+    }
+    *net = 1;
+    float* const b[5] = {h->theta2, h->target2, h->m2, h->v2, h->grad2};
+    return b[which - MDP_CRITIC2];
+  }
+  int region;
+  if (region_for(which, &region, net)) {
+    fail(h, "bad param set id");
+    return nullptr;
+  }
+  return (float*)(h->arena + h->L.off[region]);
 }
 
 const NDesc& net_of(mdp_handle* h, int agent, int net) {
@@ -1038,6 +1076,107 @@ int do_update_dp(mdp_handle* h, int agent, const int32_t* idx, const float* u_tg
   return do_apply(h, agent, 0, false, scale);
 }
 
+// ---- MATD3
+// critic 2's optimizer step: critic 1's arguments with every pointer swapped
+// into the TD3 buffer (its own sync area, no Polyak, its own stats block)
+FusedApplyArgs td3_fused_args(mdp_handle* h, int agent, int bump) {
+  FusedApplyArgs f = fused_args_for(h, agent, 1);
+  ApplyArgs& a = f.ap;
+  a.theta = h->theta2;
+  a.target = h->target2;
+  a.m = h->m2;
+  a.v = h->v2;
+  a.grad = h->grad2;
+  a.slab = h->slab2;
+  a.beta = h->beta2 + agent * 4;
+  a.polyak = 0;
+  a.slab_stat = h->stat2;
+  a.y = h->y;
+  a.stats_out = h->stats2 + agent * 8;
+  a.ticket = h->ticket2;
+  a.bump_ctr = bump;
+  f.sync_ctr = h->ra_ctr2 + (int64_t)agent * 8 * 32;
+  f.done_ctr = f.sync_ctr + 6 * 32;
+  f.sync_part = h->ra_part2 + (int64_t)agent * 6 * MDP_RA_MAXCH * 2;
+  return f;
+}
+
+int td3_step2(mdp_handle* h, int agent, bool fused, int bump) {
+  const FusedApplyArgs f = td3_fused_args(h, agent, bump);
+  if (fused) {
+    ProfScope p(h, MDP_K_REDUCE_APPLY);
+    HIPCHK(h, mdp_launch_reduce_apply(f, h->stream));
+    return 0;
+  }
+  const NDesc& d = net_of(h, agent, 1);
+  ReduceArgs r;
+  r.slab = h->slab2;
+  r.nwg = h->L.nwg;
+  r.slab_stride = h->L.slab_c;
+  r.grad = h->grad2;
+  r.off = d.off;
+  r.size = d.size;
+  r.beta = f.ap.beta;
+  r.b1 = h->cfg.adam_b1;
+  r.b2 = h->cfg.adam_b2;
+  r.ctl = h->ctl;
+  r.bump_ctr = bump;
+  {
+    ProfScope p(h, MDP_K_REDUCE);
+    HIPCHK(h, mdp_launch_reduce(r, h->stream));
+  }
+  ApplyArgs a = f.ap;
+  a.slab = nullptr;
+  a.bump_ctr = 0;
+  ProfScope p(h, MDP_K_APPLY);
+  HIPCHK(h, mdp_launch_apply(a, h->stream));
+  return 0;
+}
+
+// agent's k-th update since enable: the twin critic launch, both critics'
+// optimizer steps, and every td3_delay-th time the actor step + Polyak of all
+// three targets.  A critic-only update advances the noise counter in critic
+// 2's optimizer launch (the actor's optimizer launch does otherwise).
+int do_update_td3(mdp_handle* h, int agent, const int32_t* idx, const float* u_tgt, const float* u_act) {
+  const int64_t k = ++h->td3_work[agent];
+  const bool actor_due = k % h->td3_delay == 0;
+  const bool fused = h->fused_apply && reduce_apply_ok(h, agent, 0) && reduce_apply_ok(h, agent, 1);
+  int rc;
+  {
+    CriticArgsTwin t;
+    static_cast<CriticArgs&>(t) = critic_args(h, agent, idx, u_tgt, false, -1, nullptr, false);
+    while (t.group > 1 && lds_critic_twin_bytes(h->L.topo, t.group) > MDP_LDS_BUDGET) --t.group;
+    const int lds = lds_critic_twin_bytes(h->L.topo, t.group);
+    if (lds > MDP_LDS_BUDGET) return fail(h, "MATD3 critic step does not fit in LDS");
+    t.theta2 = h->theta2;
+    t.target2 = h->target2;
+    t.slab2 = h->slab2;
+    t.slab_stat2 = h->stat2;
+    ProfScope p(h, MDP_K_CRITIC_GRAD);
+    HIPCHK(h, mdp_launch_critic_grad_twin(t, h->L.topo.H, lds, h->stream));
+  }
+  if (fused) {
+    if ((rc = do_reduce_apply(h, agent, 1))) return rc;
+  } else {
+    if ((rc = do_reduce(h, agent, 1))) return rc;
+    if ((rc = do_apply(h, agent, 1, false, 1.0f))) return rc;
+  }
+  if ((rc = td3_step2(h, agent, fused, actor_due ? 0 : 1))) return rc;
+  if (!actor_due) return 0;
+  if ((rc = do_actor_grad(h, agent, idx, u_act))) return rc;
+  if (fused) {
+    if ((rc = do_reduce_apply(h, agent, 0))) return rc;
+  } else {
+    if ((rc = do_reduce(h, agent, 0))) return rc;
+    if ((rc = do_apply(h, agent, 0, false, 1.0f))) return rc;
+  }
+  const NDesc& d = net_of(h, agent, 1);
+  const ApplyArgs a = apply_args(h, agent, 0, 1.0f);
+  ProfScope p(h, MDP_K_APPLY);
+  HIPCHK(h, mdp_launch_polyak(h->target2 + d.off, h->theta2 + d.off, d.size, a.pa, a.pb, h->ctl, h->stream));
+  return 0;
+}
+
 // pf_out: the critic kernel also draws the next round's indices there (fast path only)
 // post_prev >= 0: this critic step finishes the work that agent post_prev's
 // actor launch started (critic_post); pre_next >= 0: this actor launch starts
@@ -1048,6 +1187,7 @@ int do_update(mdp_handle* h, int agent, const int32_t* idx, const float* u_tgt, 
   // data parallel: the exchange runs whatever the noise source (injected
   // uniforms included -- an update that skipped it would split the replicas)
   if (h->comm || h->p2p) return do_update_dp(h, agent, idx, u_tgt, u_act, pf_out, post_prev, pre_next, pre_idx, dp);
+  if (h->td3) return do_update_td3(h, agent, idx, u_tgt, u_act);
   int rc;
   const bool fused = h->fused_apply && reduce_apply_ok(h, agent, 0) && reduce_apply_ok(h, agent, 1);
   const bool pre = actor_pre_ok(h, agent);
@@ -1466,6 +1606,35 @@ int per_update(mdp_handle* h, int agent0, int agents, int count, const int32_t* 
 }
 
 const char* kPerNoDp = "prioritized replay runs on one GPU in strict mode: no data-parallel exchange";
+const char* kTd3NoDp = "MATD3 (mdp_td3_enable) runs on one GPU in strict mode: no data-parallel exchange";
+
+// byte offsets inside the caller's TD3 buffer
+struct Td3Layout {
+  int64_t theta, target, m, v, grad, slab, stat, beta, stats, ticket, ctr, part, total;
+};
+Td3Layout td3_layout(const mdp_config& c, const Layout& L) {
+  Td3Layout t;
+  int64_t o = 0;
+  auto take = [&](int64_t bytes) {
+    const int64_t at = o;
+    o += a256(bytes);
+    return at;
+  };
+  t.theta = take(4 * L.PT);
+  t.target = take(4 * L.PT);
+  t.m = take(4 * L.PT);
+  t.v = take(4 * L.PT);
+  t.grad = take(4 * L.PT);
+  t.slab = take(4 * (int64_t)L.nwg * L.slab_c);
+  t.stat = take(8 * 8 * (int64_t)L.nwg);
+  t.beta = take(4 * 4 * (int64_t)c.n_agents);
+  t.stats = take(8 * 8 * (int64_t)c.n_agents);
+  t.ticket = take(256);
+  t.ctr = take((int64_t)MDP_MAX_AGENTS * 8 * 128);          // per agent 8 counters x 128 B (mdp_ra_sync_bytes)
+  t.part = take((int64_t)MDP_MAX_AGENTS * 6 * MDP_RA_MAXCH * 16);
+  t.total = o;
+  return t;
+}
 
 }  // namespace
 
@@ -1631,6 +1800,7 @@ int mdp_destroy(mdp_handle* h) {
   xgmi_release(h);
   for (auto& kv : h->step_exec) (void)hipGraphExecDestroy(kv.second);
   for (auto& kv : h->multi_exec) (void)hipGraphExecDestroy(kv.second);
+  for (auto& kv : h->td3_exec) (void)hipGraphExecDestroy(kv.second);
   if (h->round_graph) (void)hipGraphDestroy(h->round_graph);
   if (h->own_stream && h->stream) (void)hipStreamDestroy(h->stream);
   delete h;
@@ -1708,13 +1878,14 @@ int mdp_row_layout(const mdp_handle* h, int32_t agent, int32_t out6[6]) {
 
 int mdp_set_params(mdp_handle* h, int32_t agent, int32_t which, const float* src, int64_t n) {
   if (bad_agent(h, agent)) return -1;
-  int region, net;
-  if (region_for(which, &region, &net)) return fail(h, "bad param set id");
+  int net;
+  float* base = which_base(h, which, &net);
+  if (!base) return -1;
   const NDesc& d = net_of(h, agent, net);
   if (n != net_floats(h, agent, net)) return fail(h, "param count mismatch");
   h->started = true;
   const std::vector<float> buf = scatter_net(h, agent, net, src);
-  float* dst = (float*)(h->arena + h->L.off[region]) + d.off;
+  float* dst = base + d.off;
   HIPCHK(h, hipMemcpyAsync(dst, buf.data(), 4 * buf.size(), hipMemcpyHostToDevice, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
   return 0;
@@ -1722,12 +1893,13 @@ int mdp_set_params(mdp_handle* h, int32_t agent, int32_t which, const float* src
 
 int mdp_get_params(mdp_handle* h, int32_t agent, int32_t which, float* dst, int64_t n) {
   if (bad_agent(h, agent)) return -1;
-  int region, net;
-  if (region_for(which, &region, &net)) return fail(h, "bad param set id");
+  int net;
+  const float* base = which_base(h, which, &net);
+  if (!base) return -1;
   const NDesc& d = net_of(h, agent, net);
   if (n != net_floats(h, agent, net)) return fail(h, "param count mismatch");
   std::vector<float> buf(d.size);
-  const float* src = (const float*)(h->arena + h->L.off[region]) + d.off;
+  const float* src = base + d.off;
   HIPCHK(h, hipMemcpyAsync(buf.data(), src, 4 * buf.size(), hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
   int64_t s = 0;
@@ -1744,14 +1916,18 @@ int mdp_get_params(mdp_handle* h, int32_t agent, int32_t which, float* dst, int6
 
 int mdp_get_beta_powers(mdp_handle* h, int32_t agent, int32_t net, float out2[2]) {
   if (bad_agent(h, agent)) return -1;
-  HIPCHK(h, hipMemcpyAsync(out2, h->beta + agent * 8 + (net ? 4 : 0), 8, hipMemcpyDeviceToHost, h->stream));
+  if (net == 2 && !h->td3) return fail(h, "mdp_get_beta_powers: net 2 (the second critic) needs MATD3 (mdp_td3_enable)");
+  const float* src = net == 2 ? h->beta2 + agent * 4 : h->beta + agent * 8 + (net ? 4 : 0);
+  HIPCHK(h, hipMemcpyAsync(out2, src, 8, hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
   return 0;
 }
 
 int mdp_set_beta_powers(mdp_handle* h, int32_t agent, int32_t net, const float in2[2]) {
   if (bad_agent(h, agent)) return -1;
-  HIPCHK(h, hipMemcpyAsync(h->beta + agent * 8 + (net ? 4 : 0), in2, 8, hipMemcpyHostToDevice, h->stream));
+  if (net == 2 && !h->td3) return fail(h, "mdp_set_beta_powers: net 2 (the second critic) needs MATD3 (mdp_td3_enable)");
+  float* dst = net == 2 ? h->beta2 + agent * 4 : h->beta + agent * 8 + (net ? 4 : 0);
+  HIPCHK(h, hipMemcpyAsync(dst, in2, 8, hipMemcpyHostToDevice, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
   return 0;
 }
@@ -1941,6 +2117,51 @@ int mdp_q_values(mdp_handle* h, int32_t agent, int32_t target, const float* x_de
 }
 
 // ---------------------------------------------------------------- training
+// MATD3's host counters: the launches about to be issued or captured count from
+// the committed state; td3_commit after they (or a graph replay of them) went out
+static void td3_begin(mdp_handle* h) {
+  for (int i = 0; i < MDP_MAX_AGENTS; ++i) h->td3_work[i] = h->td3_count[i];
+}
+static void td3_commit(mdp_handle* h, int rounds) {
+  if (!h->td3) return;
+  for (int i = 0; i < h->cfg.n_agents; ++i) h->td3_count[i] += rounds;
+}
+// key of a TD3 graph: what is captured depends on which agents are due for an actor step
+static std::vector<int> td3_key(const mdp_handle* h, int kind, const std::vector<int>& ks) {
+  std::vector<int> key{kind};
+  for (int i = 0; i < h->cfg.n_agents; ++i) key.push_back((int)(h->td3_count[i] % h->td3_delay));
+  key.insert(key.end(), ks.begin(), ks.end());
+  return key;
+}
+// the graph of `body` under `key`, captured on first use (counting from the committed state)
+static int td3_graph(mdp_handle* h, const std::vector<int>& key, const std::function<int()>& body,
+                     hipGraphExec_t* out) {
+  auto it = h->td3_exec.find(key);
+  if (it != h->td3_exec.end()) {
+    *out = it->second;
+    return 0;
+  }
+  td3_begin(h);
+  HIPCHK(h, hipStreamBeginCapture(h->stream, hipStreamCaptureModeThreadLocal));
+  h->capturing = true;
+  const int rc = body();
+  h->capturing = false;
+  hipGraph_t g = nullptr;
+  const hipError_t e = hipStreamEndCapture(h->stream, &g);
+  if (rc) {
+    if (g) (void)hipGraphDestroy(g);
+    return rc;
+  }
+  if (e != hipSuccess) return fail(h, "hipStreamEndCapture", e);
+  hipGraphExec_t x = nullptr;
+  const hipError_t ei = hipGraphInstantiate(&x, g, nullptr, nullptr, 0);
+  (void)hipGraphDestroy(g);
+  if (ei != hipSuccess) return fail(h, "hipGraphInstantiate", ei);
+  h->td3_exec.emplace(key, x);
+  *out = x;
+  return 0;
+}
+
 int mdp_update_gate(mdp_handle* h, int64_t t) {
   MDP_NEED(h);
   if (h->len < (int64_t)h->cfg.batch_size * h->cfg.max_episode_len) return 1;  // maddpg.py:162-163
@@ -1973,7 +2194,10 @@ int mdp_update(mdp_handle* h, int32_t agent, const int32_t* idx_dev, const float
     if (rc) return rc;
     idx = slot;
   }
-  return do_update(h, agent, idx, u_tgt_dev, u_act_dev);
+  td3_begin(h);
+  const int rc = do_update(h, agent, idx, u_tgt_dev, u_act_dev);
+  if (!rc && h->td3) h->td3_count[agent] += 1;
+  return rc;
 }
 
 int mdp_agent_update(mdp_handle* h, int32_t agent, int64_t t, const int32_t* idx_dev, const float* u_dev,
@@ -2115,7 +2339,18 @@ int mdp_update_round(mdp_handle* h) {
   h->trained = true;
   if (!h->graphs || any_prof(h) || h->eager_rounds < 1) {
     ++h->eager_rounds;  // the first round runs eagerly (one-time kernel attribute setup)
-    return round_launches(h);
+    td3_begin(h);
+    const int rc = round_launches(h);
+    if (!rc) td3_commit(h, 1);
+    return rc;
+  }
+  if (h->td3) {
+    hipGraphExec_t x = nullptr;
+    const int rc = td3_graph(h, td3_key(h, 0, {}), [&] { return round_launches(h); }, &x);
+    if (rc) return rc;
+    HIPCHK(h, hipGraphLaunch(x, h->stream));
+    td3_commit(h, 1);
+    return 0;
   }
   if (!h->round_exec) {
     HIPCHK(h, hipStreamBeginCapture(h->stream, hipStreamCaptureModeThreadLocal));
@@ -2152,6 +2387,7 @@ int mdp_dp_unique_id(uint8_t* out128) {
 int mdp_dp_init(mdp_handle* h, const uint8_t* id128, int32_t world, int32_t rank) {
   if (unusable(h) || !id128) return -1;
   if (h->per) return fail(h, kPerNoDp);
+  if (h->td3) return fail(h, (std::string("mdp_dp_init: ") + kTd3NoDp).c_str());
   if (h->update_mode != 0) return fail(h, "join data parallelism before choosing the throughput mode");
   if (h->p2p || h->xbuf) return fail(h, "mdp_dp_init: the xGMI exchange is already set up");
   if (!rccl().ok) return fail(h, "librccl.so.1 could not be loaded");
@@ -2190,6 +2426,7 @@ static void drop_graphs(mdp_handle* h);
 int mdp_dp_xgmi_open(mdp_handle* h, int32_t world, int32_t rank, uint8_t* handle_out) {
   if (unusable(h) || !handle_out) return -1;
   if (h->per) return fail(h, kPerNoDp);
+  if (h->td3) return fail(h, (std::string("mdp_dp_xgmi_open: ") + kTd3NoDp).c_str());
   if (h->update_mode != 0) return fail(h, "join data parallelism before choosing the throughput mode");
   if (h->comm) return fail(h, "mdp_dp_xgmi_open: an RCCL communicator is already set up");
   if (h->xbuf) return fail(h, "mdp_dp_xgmi_open: already open");
@@ -2264,6 +2501,7 @@ int mdp_dp_xgmi_enable(mdp_handle* h) {
   if (unusable(h)) return -1;
   if (!h->xd_dev) return fail(h, "mdp_dp_xgmi_enable: not connected");
   if (h->per) return fail(h, kPerNoDp);
+  if (h->td3) return fail(h, (std::string("mdp_dp_xgmi_enable: ") + kTd3NoDp).c_str());
   if (h->update_mode != 0) return fail(h, "join data parallelism before choosing the throughput mode");
   HIPCHK(h, hipStreamSynchronize(h->stream));
   h->p2p = true;
@@ -2333,8 +2571,10 @@ int mdp_set_graphs(mdp_handle* h, int32_t on) {
 static void drop_graphs(mdp_handle* h) {
   for (auto& kv : h->step_exec) (void)hipGraphExecDestroy(kv.second);
   for (auto& kv : h->multi_exec) (void)hipGraphExecDestroy(kv.second);
+  for (auto& kv : h->td3_exec) (void)hipGraphExecDestroy(kv.second);
   h->step_exec.clear();
   h->multi_exec.clear();
+  h->td3_exec.clear();
   h->eager_steps = 0;
   if (h->round_exec) {
     (void)hipGraphExecDestroy(h->round_exec);
@@ -2351,6 +2591,7 @@ int mdp_set_update_mode(mdp_handle* h, int32_t mode) {
   if (unusable(h)) return -1;
   if (mode != 0 && mode != 1) return fail(h, "update mode must be 0 (strict) or 1 (throughput)");
   if (mode == 1) {
+    if (h->td3) return fail(h, "mdp_set_update_mode: mode 1 (throughput) is not supported with MATD3 (mdp_td3_enable)");
     if (h->per) return fail(h, "prioritized replay needs the strict update mode (throughput mode is not supported)");
     if (!tp_ok(h)) return fail(h, "throughput mode needs the fused optimizer step for every net and <= 8 agents");
     HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -2366,6 +2607,7 @@ int mdp_set_update_mode(mdp_handle* h, int32_t mode) {
 
 int mdp_update_all(mdp_handle* h, const int32_t* idx_dev, const float* u_tgt_dev, const float* u_act_dev) {
   if (unusable(h)) return -1;
+  if (h->td3) return fail(h, "mdp_update_all: throughput mode is not supported with MATD3 (mdp_td3_enable)");
   if (h->update_mode != 1) return fail(h, "mdp_update_all: set throughput mode first");
   h->trained = true;
   if (h->len <= 0) return fail(h, "update on an empty replay buffer");
@@ -2384,10 +2626,17 @@ int mdp_update_all(mdp_handle* h, const int32_t* idx_dev, const float* u_tgt_dev
   return do_round_tp(h, idx, u_tgt_dev, u_act_dev, nullptr);
 }
 
+static const char* kTd3NoPhase(const char* fn) {
+  static thread_local std::string m;
+  m = std::string(fn) + ": the phase entry points serve data parallelism; MATD3 (mdp_td3_enable) uses mdp_update";
+  return m.c_str();
+}
+
 int mdp_critic_grad(mdp_handle* h, int32_t agent, const int32_t* idx_dev, const float* u_tgt_dev) {
   if (bad_agent(h, agent)) return -1;
   if (!idx_dev) return fail(h, "critic_grad needs indices");
   if (h->per) return fail(h, "mdp_critic_grad: the phase entry points serve data parallelism; prioritized replay uses mdp_update");
+  if (h->td3) return fail(h, kTd3NoPhase("mdp_critic_grad"));
   h->trained = true;
   MDP_DEV(h, idx_dev, 4 * (int64_t)h->cfg.batch_size, "mdp_critic_grad", false);
   MDP_DEV(h, u_tgt_dev, 4 * (int64_t)h->cfg.n_agents * h->cfg.batch_size * MDP_ACT_DIM, "mdp_critic_grad", true);
@@ -2397,6 +2646,7 @@ int mdp_critic_grad(mdp_handle* h, int32_t agent, const int32_t* idx_dev, const 
 int mdp_actor_grad(mdp_handle* h, int32_t agent, const int32_t* idx_dev, const float* u_act_dev) {
   if (bad_agent(h, agent)) return -1;
   if (!idx_dev) return fail(h, "actor_grad needs indices");
+  if (h->td3) return fail(h, kTd3NoPhase("mdp_actor_grad"));
   h->started = true;
   MDP_DEV(h, idx_dev, 4 * (int64_t)h->cfg.batch_size, "mdp_actor_grad", false);
   MDP_DEV(h, u_act_dev, 4 * (int64_t)h->cfg.batch_size * MDP_ACT_DIM, "mdp_actor_grad", true);
@@ -2405,11 +2655,13 @@ int mdp_actor_grad(mdp_handle* h, int32_t agent, const int32_t* idx_dev, const f
 
 int mdp_reduce_grad(mdp_handle* h, int32_t agent, int32_t net) {
   if (bad_agent(h, agent)) return -1;
+  if (h->td3) return fail(h, kTd3NoPhase("mdp_reduce_grad"));
   return do_reduce(h, agent, net ? 1 : 0);
 }
 
 int mdp_apply_grad(mdp_handle* h, int32_t agent, int32_t net, float scale) {
   if (bad_agent(h, agent)) return -1;
+  if (h->td3) return fail(h, kTd3NoPhase("mdp_apply_grad"));
   return do_apply(h, agent, net ? 1 : 0, false, scale);
 }
 
@@ -2742,6 +2994,14 @@ static int step_launches(mdp_handle* h, int rounds) {
     for (int r = 0; r < rounds && !rc; ++r) rc = per_round_launches(h, r == 0);
     return rc;
   }
+  if (h->td3) {  // MATD3: one n B draw per round, no draw rides on another launch
+    int rc = env_step_launch(h, nullptr, nullptr);
+    for (int r = 0; r < rounds && !rc; ++r) {
+      if ((rc = launch_make_index(h, nb, h->index))) break;
+      rc = round_updates(h, h->index);
+    }
+    return rc;
+  }
   int32_t* slot[2] = {h->index, h->index + nb};
   // the critic-launch prefetch serves throughput mode only where its one critic
   // launch covers every agent (tp_fast); a mix of fast and general agents
@@ -2777,7 +3037,18 @@ static int train_step_body(mdp_handle* h, int rounds) {
   const bool no_graph = h->comm && !h->dp_graphs;
   if (!h->graphs || no_graph || any_prof(h) || h->eager_steps < 1 || rounds == 0) {
     if (rounds > 0) ++h->eager_steps;  // first training step eager (one-time kernel attribute setup)
-    return step_launches(h, rounds);
+    td3_begin(h);
+    const int rc = step_launches(h, rounds);
+    if (!rc) td3_commit(h, rounds);
+    return rc;
+  }
+  if (h->td3) {
+    hipGraphExec_t x = nullptr;
+    const int rc = td3_graph(h, td3_key(h, 1, {rounds}), [&] { return step_launches(h, rounds); }, &x);
+    if (rc) return rc;
+    HIPCHK(h, hipGraphLaunch(x, h->stream));
+    td3_commit(h, rounds);
+    return 0;
   }
   auto it = h->step_exec.find(rounds);
   if (it == h->step_exec.end()) {
@@ -2806,7 +3077,9 @@ static int train_step_body(mdp_handle* h, int rounds) {
 // round counts): the launches are exactly those of the steps one by one, but a
 // graph launch boundary costs ~6.7 us on the GPU clock against ~1.5-2 us for a
 // kernel boundary inside a graph (tools/step_boundary.py)
+static int multi_body(mdp_handle* h, const std::vector<int>& ks);
 static int multi_graph(mdp_handle* h, const std::vector<int>& ks, hipGraphExec_t* out) {
+  if (h->td3) return td3_graph(h, td3_key(h, 2, ks), [&] { return multi_body(h, ks); }, out);
   auto it = h->multi_exec.find(ks);
   if (it != h->multi_exec.end()) {
     *out = it->second;
@@ -2814,20 +3087,7 @@ static int multi_graph(mdp_handle* h, const std::vector<int>& ks, hipGraphExec_t
   }
   HIPCHK(h, hipStreamBeginCapture(h->stream, hipStreamCaptureModeThreadLocal));
   h->capturing = true;
-  int rc = 0;
-  for (size_t i = 0; i < ks.size() && !rc;) {
-    // a stretch of steps without update rounds (one env copy: 99 of every 100)
-    // as one rollout launch of that many steps, when the envs fit one workgroup
-    size_t j = i;
-    while (j < ks.size() && ks[j] == 0 && (int)(j - i) < 64) ++j;
-    if (j - i > 1 && rollout_multi_ok(h)) {
-      rc = env_step_launch(h, nullptr, nullptr, nullptr, nullptr, 0, (int)(j - i));
-      i = j;
-    } else {
-      rc = step_launches(h, ks[i]);
-      ++i;
-    }
-  }
+  const int rc = multi_body(h, ks);
   h->capturing = false;
   hipGraph_t g = nullptr;
   const hipError_t e = hipStreamEndCapture(h->stream, &g);
@@ -2843,6 +3103,25 @@ static int multi_graph(mdp_handle* h, const std::vector<int>& ks, hipGraphExec_t
   h->multi_exec.emplace(ks, x);
   *out = x;
   return 0;
+}
+
+// the launches of a group of consecutive training steps
+static int multi_body(mdp_handle* h, const std::vector<int>& ks) {
+  int rc = 0;
+  for (size_t i = 0; i < ks.size() && !rc;) {
+    // a stretch of steps without update rounds (one env copy: 99 of every 100)
+    // as one rollout launch of that many steps, when the envs fit one workgroup
+    size_t j = i;
+    while (j < ks.size() && ks[j] == 0 && (int)(j - i) < 64) ++j;
+    if (j - i > 1 && rollout_multi_ok(h)) {
+      rc = env_step_launch(h, nullptr, nullptr, nullptr, nullptr, 0, (int)(j - i));
+      i = j;
+    } else {
+      rc = step_launches(h, ks[i]);
+      ++i;
+    }
+  }
+  return rc;
 }
 
 int mdp_train_steps(mdp_handle* h, int32_t n, const int32_t* rounds, int32_t launch) {
@@ -2879,6 +3158,10 @@ int mdp_train_steps(mdp_handle* h, int32_t n, const int32_t* rounds, int32_t lau
   if (rc) {
     h->len = len0;
     h->next = next0;
+  } else {
+    int total = 0;
+    for (int k : ks) total += k;
+    td3_commit(h, total);
   }
   return rc;
 }
@@ -2980,6 +3263,10 @@ int mdp_check_finite(mdp_handle* h, int64_t* nonfinite) {
   HIPCHK(h, hipMemsetAsync(&h->ctl->nonfinite, 0, sizeof(uint32_t), h->stream));
   const float* sets[4] = {h->theta, h->target, h->m, h->v};
   for (const float* p : sets) HIPCHK(h, mdp_launch_count_nonfinite(p, h->L.PT, &h->ctl->nonfinite, h->stream));
+  if (h->td3) {  // the second critic's sets (actor spans of its regions stay zero)
+    const float* twin[4] = {h->theta2, h->target2, h->m2, h->v2};
+    for (const float* p : twin) HIPCHK(h, mdp_launch_count_nonfinite(p, h->L.PT, &h->ctl->nonfinite, h->stream));
+  }
   uint32_t c = 0;
   const int n = h->cfg.n_agents;
   std::vector<double> st(8 * (size_t)n);
@@ -3028,6 +3315,7 @@ int mdp_per_enable(mdp_handle* h, void* buf_dev, int64_t bytes, float alpha, flo
                    float abs_err_upper) {
   MDP_NEED(h);
   if (h->per) return fail(h, "mdp_per_enable: already enabled");
+  if (h->td3) return fail(h, "mdp_per_enable: prioritized replay and MATD3 (mdp_td3_enable) do not combine");
   if (h->trained)
     return fail(h, "mdp_per_enable: call it before the handle's first update or train call");
   if (h->update_mode != 0)
@@ -3070,6 +3358,75 @@ int mdp_per_enable(mdp_handle* h, void* buf_dev, int64_t bytes, float alpha, flo
     h->per = false;
     return -1;
   }
+  return 0;
+}
+
+// ------------------------------------------------------------------ MATD3
+int64_t mdp_td3_bytes(const mdp_config* cfg) {
+  Layout L;
+  std::string err;
+  if (!build_layout(cfg, L, err)) return -1;
+  return td3_layout(*cfg, L).total;
+}
+
+int mdp_td3_enable(mdp_handle* h, void* buf_dev, int64_t bytes, int32_t policy_delay) {
+  MDP_NEED(h);
+  if (h->td3) return fail(h, "mdp_td3_enable: already enabled");
+  if (h->trained) return fail(h, "mdp_td3_enable: call it before the handle's first update, round or train call");
+  if (policy_delay < 1 || policy_delay > 8) return fail(h, "mdp_td3_enable: policy_delay must be in 1..8");
+  if (h->per) return fail(h, "mdp_td3_enable: MATD3 and prioritized replay (mdp_per_enable) do not combine");
+  if (h->update_mode != 0)
+    return fail(h, "mdp_td3_enable: MATD3 needs the strict update mode (throughput mode is not supported)");
+  if (h->comm || h->p2p || h->xbuf || h->cfg.world_size > 1)
+    return fail(h, (std::string("mdp_td3_enable: ") + kTd3NoDp).c_str());
+  const Td3Layout tl = td3_layout(h->cfg, h->L);
+  if (!buf_dev) return fail(h, "mdp_td3_enable: buf_dev is null");
+  if (bytes < tl.total) return fail(h, "mdp_td3_enable: bytes is smaller than mdp_td3_bytes");
+  if (lds_critic_twin_bytes(h->L.topo, 1) > MDP_LDS_BUDGET)
+    return fail(h, "mdp_td3_enable: the twin critic step does not fit the kernels' LDS envelope");
+  MDP_DEV(h, buf_dev, tl.total, "mdp_td3_enable", false);
+  char* b = (char*)buf_dev;
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  HIPCHK(h, hipMemsetAsync(b, 0, tl.total, h->stream));
+  std::vector<float> beta(4 * (size_t)h->cfg.n_agents);
+  for (int i = 0; i < h->cfg.n_agents; ++i) {  // as mdp_create: the powers start at beta
+    beta[4 * i] = beta[4 * i + 2] = h->cfg.adam_b1;
+    beta[4 * i + 1] = beta[4 * i + 3] = h->cfg.adam_b2;
+  }
+  HIPCHK(h, hipMemcpyAsync(b + tl.beta, beta.data(), 4 * beta.size(), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  h->theta2 = (float*)(b + tl.theta);
+  h->target2 = (float*)(b + tl.target);
+  h->m2 = (float*)(b + tl.m);
+  h->v2 = (float*)(b + tl.v);
+  h->grad2 = (float*)(b + tl.grad);
+  h->slab2 = (float*)(b + tl.slab);
+  h->stat2 = (double*)(b + tl.stat);
+  h->beta2 = (float*)(b + tl.beta);
+  h->stats2 = (double*)(b + tl.stats);
+  h->ticket2 = (uint32_t*)(b + tl.ticket);
+  h->ra_ctr2 = (uint32_t*)(b + tl.ctr);
+  h->ra_part2 = (uint64_t*)(b + tl.part);
+  h->td3_delay = policy_delay;
+  for (int i = 0; i < MDP_MAX_AGENTS; ++i) h->td3_count[i] = h->td3_work[i] = 0;
+  h->td3 = true;
+  h->general_grads = true;  // MATD3 runs on the general kernels: no actor_pre / critic_pre, no index prefetch
+  drop_graphs(h);
+  return 0;
+}
+
+int mdp_td3_info(mdp_handle* h, int32_t agent, double out4[4]) {
+  if (bad_agent(h, agent)) return -1;
+  if (!h->td3) return fail(h, "mdp_td3_info: MATD3 is not enabled (mdp_td3_enable)");
+  if (!out4) return fail(h, "mdp_td3_info: out4 is null");
+  double q1 = 0.0, q2 = 0.0;
+  HIPCHK(h, hipMemcpyAsync(&q1, h->stats + agent * 8, 8, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipMemcpyAsync(&q2, h->stats2 + agent * 8, 8, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  out4[0] = (double)h->td3_count[agent];
+  out4[1] = (double)(h->td3_count[agent] / h->td3_delay);
+  out4[2] = q1;
+  out4[3] = q2;
   return 0;
 }
 

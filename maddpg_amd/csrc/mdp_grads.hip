@@ -20,6 +20,9 @@
 //   gather | L1 tiles of the target actors (+ critic) || L2 tiles || heads, Gumbel a~
 //   || target critic L1 || L2 || wave 0: head, fp64 TD, loss, dL/dq
 //   || dW3, db3, d2 || dh1 tiles + dW2 tiles || dW1, db1
+// k_critic_grad<.., TWIN> (MATD3): the same up to the target critic, then
+//   || target critic 2 L1 || L2 || wave 0: heads, y from min(q1', q2'), Q1's loss seed
+//   || Q1 backward || Q2 forward L1 || L2 || head, loss seed on the same y || Q2 backward
 // k_actor_grad (maddpg.py:37-58):
 //   gather | actor L1 || L2 || head, Gumbel a_i, critic input || critic L1 || L2
 //   || head q, d2 || dh1c tiles || da, softmax backward + reg (wave 0)
@@ -348,9 +351,49 @@ __device__ __forceinline__ void wgrad_tile(const float* X, int ldx, int K, const
 
 static_assert(MDP_GEN_THREADS / 64 >= MDP_MAX_UNITS / 16, "one single-net layer tile per wave (pf_load / *_pf)");
 
+// Backward through one critic (tf.gradients of q_loss w.r.t. q_func vars) from the
+// loss seed dq and the forward's h1c / h2c, with the first W2^T chunk (pft) and
+// this thread's W3 column (w3) issued ahead by the caller; partial gradients
+// into this workgroup's slab (net-relative).  d2 / d1: two free activation slots
+template <int H>
+__device__ __forceinline__ void critic_backward(const float* th, const NDesc& nd, float* slab, const float* dq,
+                                                const float* h1c, const float* h2c, float* d2, float* d1,
+                                                const float* Xc, int ldX, int cin, const float w3, f32x4 (&pft)[4],
+                                                const int tid, const int wave, const int nw) {
+  constexpr int NT = H / 16;
+  const int ldh = H + 1;
+  if (tid < H) {
+    float s = 0.f;
+    for (int r = 0; r < MDP_R; ++r) s = fmaf(h2c[r * ldh + tid], dq[r], s);
+    slab[nd.t[4].off + tid] = s;
+  }
+  if (tid == H) {
+    float s = 0.f;
+    for (int r = 0; r < MDP_R; ++r) s += dq[r];
+    slab[nd.t[5].off] = s;
+  }
+  for (int r = tid / H, h = tid % H; r < MDP_R; r += MDP_GEN_THREADS / H)
+    d2[r * ldh + h] = h2c[r * ldh + h] > 0.f ? dq[r] * w3 : 0.f;
+  __syncthreads();
+  MDP_STAMP(4);
+  // dh1 tiles then dW2 tiles, dealt over all waves
+  for (int t = wave; t < NT + NT * NT; t += nw) {
+    if (t < NT) dgrad_tile_relu_pf(d2, ldh, H, th + nd.t[2].off, h1c, ldh, d1, ldh, t, pft);
+    else wgrad_tile(h1c, ldh, H, d2, ldh, H, slab + nd.t[2].off, t - NT);
+  }
+  colsum16(d2, ldh, H, slab + nd.t[3].off);
+  __syncthreads();
+  wgrad_waves(Xc, ldX, cin, d1, ldh, H, slab + nd.t[0].off, 0, nw);
+  colsum16(d1, ldh, H, slab + nd.t[1].off);
+}
+
+
 // blk: this workgroup's row tile (blockIdx.x, or its index inside the
 // critic half of a gradient-pair launch)
-template <int H, bool PER = false, class A = CriticArgs>
+// TWIN (A = CriticArgsTwin): the MATD3 step -- both target critics on the same
+// [o' | a~], y from the smaller, then critic 1's and critic 2's loss seed and
+// backward one after the other on the same activation slots
+template <int H, bool PER = false, class A = CriticArgs, bool TWIN = false>
 __device__ __forceinline__ void critic_body(const A& a, const Topo& T, const int blk) {
   // (no MDP_KARG_TOUCH here: at H = 128 it turned the kernel's 47 spilled
   // SGPRs into 91 spilled VGPRs)
@@ -370,6 +413,8 @@ __device__ __forceinline__ void critic_body(const A& a, const Topo& T, const int
   float* dq = cv.take(MDP_R);
   int* cnt = reinterpret_cast<int*>(cv.take(MDP_MAX_AGENTS + 4));  // layer-1 units done per net, then the
                                                                     // work-queue counter (fwd_phase_l12)
+  float* ys = nullptr;  // TWIN: the rows' fp32 TD target, kept for critic 2's loss seed
+  if constexpr (TWIN) ys = cv.take(MDP_R);
 
   const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63, nw = blockDim.x >> 6;
   const int r0 = blk * MDP_R;
@@ -571,9 +616,31 @@ __device__ __forceinline__ void critic_body(const A& a, const Topo& T, const int
     if (wave < NT) {
       if (H / 4 <= 32 && wave == 0) head_load<HKS>(thw, thb, P + nd.t[4].off, P + nd.t[5].off, 1);
       fwd_tile_pf<true>(hA, ldh, 0, H, P + nd.t[2].off, P + nd.t[3].off, H, nullptr, 0, hB, ldh, wave, pf);
-      pf_load_t(pft, a.theta + nd.t[2].off, H, wave);  // the backward's dh1 = d2 W2^T
+      if constexpr (!TWIN) pf_load_t(pft, a.theta + nd.t[2].off, H, wave);  // the backward's dh1 = d2 W2^T
     }
     __syncthreads();
+    if constexpr (TWIN) {
+      // q1' off hB slot 0 (wave 0, today's head) while the tile waves run target
+      // critic 2's layer 1 on the same xt into hA slot 0 (free since the layer
+      // above); then its layer 2 into hB slot 0 and its head beside q1' in lg
+      const float* P2 = a.target2;
+      if (wave == 0) {
+        if constexpr (H / 4 <= 32) head_acc<HKS>(thw, thb, hB, ldh, 1, lg, 8);
+        else head_mfma<H / 4>(hB, ldh, H, P + nd.t[4].off, P + nd.t[5].off, 1, lg, 8);
+      }
+      if (wave < NT) {
+        pf_load(pf, P2 + nd.t[0].off, H, wave, 0, ag.cin);
+        fwd_tile_pf<true>(xt, ldc, 0, ag.cin, P2 + nd.t[0].off, P2 + nd.t[1].off, H, nullptr, 0, hA, ldh, wave, pf);
+        pf_load(pf, P2 + nd.t[2].off, H, wave, 0, H);
+      }
+      __syncthreads();
+      if (wave < NT) {
+        fwd_tile_pf<true>(hA, ldh, 0, H, P2 + nd.t[2].off, P2 + nd.t[3].off, H, nullptr, 0, hB, ldh, wave, pf);
+        pf_load_t(pft, a.theta + nd.t[2].off, H, wave);
+      }
+      __syncthreads();
+      if (wave == 0) head_mfma<H / 4>(hB, ldh, H, P2 + nd.t[4].off, P2 + nd.t[5].off, 1, lg + 1, 8);
+    }
   }
   // the dq * W3 backward below reads one W3 column per thread (the block is a
   // multiple of H wide): requested here, ahead of the TD-error phase, instead
@@ -582,15 +649,19 @@ __device__ __forceinline__ void critic_body(const A& a, const Topo& T, const int
   const float w3h = a.theta[nd.t[4].off + tid % H];
   if (wave == 0) {
     const float* P = a.target;
-    if constexpr (H / 4 <= 32) head_acc<HKS>(thw, thb, hB, ldh, 1, lg, 8);
-    else head_mfma<H / 4>(hB, ldh, H, P + nd.t[4].off, P + nd.t[5].off, 1, lg, 8);
+    if constexpr (!TWIN) {
+      if constexpr (H / 4 <= 32) head_acc<HKS>(thw, thb, hB, ldh, 1, lg, 8);
+      else head_mfma<H / 4>(hB, ldh, H, P + nd.t[4].off, P + nd.t[5].off, 1, lg, 8);
+    }
     wave_sync();
     double s_l = 0.0, s_y = 0.0, s_r = 0.0, s_q = 0.0;
     float g = 0.f;
     if (lane < nvalid) {
       const double rew = (double)rowbuf[lane * ldr + ag.rew_off];
       const double done = (double)rowbuf[lane * ldr + ag.done_off];
-      const double qn = (double)lg[lane * 8];
+      float qnf = lg[lane * 8];
+      if constexpr (TWIN) qnf = fminf(qnf, lg[lane * 8 + 1]);  // clipped double-Q
+      const double qn = (double)qnf;
       const double y64 = rew + a.gamma * (1.0 - done) * qn;
       const float y = (float)y64;
       const float diff = qv[lane * 8] - y;
@@ -606,6 +677,7 @@ __device__ __forceinline__ void critic_body(const A& a, const Topo& T, const int
       s_r = rew;
       s_q = qn;
       a.y_out[r0 + lane] = y64;
+      if constexpr (TWIN) ys[lane] = y;
     }
     if (lane < MDP_R) dq[lane] = g;
     s_l = sum16(s_l);
@@ -624,39 +696,58 @@ __device__ __forceinline__ void critic_body(const A& a, const Topo& T, const int
   MDP_STAMP(3);
 
   // backward through the critic (tf.gradients of q_loss w.r.t. q_func vars)
-  float* slab = a.slab + (int64_t)blk * a.slab_stride - nd.off;
-  float* d2 = hA;
-  float* d1 = hB;
-  if (tid < H) {
-    float s = 0.f;
-    for (int r = 0; r < MDP_R; ++r) s = fmaf(h2c[r * ldh + tid], dq[r], s);
-    slab[nd.t[4].off + tid] = s;
+  critic_backward<H>(a.theta, nd, a.slab + (int64_t)blk * a.slab_stride - nd.off, dq, h1c, h2c, hA, hB, Xc, ldX, ag.cin,
+                     w3h, pft, tid, wave, nw);
+  if constexpr (TWIN) {
+    // critic 2: forward from Xc on the slots critic 1's backward has finished
+    // with, loss seed against the same y, the same backward into slab2
+    __syncthreads();
+    const float* P2 = a.theta2;
+    if (wave < NT) {
+      pf_load(pf, P2 + nd.t[0].off, H, wave, 0, ag.cin);
+      fwd_tile_pf<true>(Xc, ldX, 0, ag.cin, P2 + nd.t[0].off, P2 + nd.t[1].off, H, nullptr, 0, h1c, ldh, wave, pf);
+      pf_load(pf, P2 + nd.t[2].off, H, wave, 0, H);
+    }
+    __syncthreads();
+    if (wave < NT) {
+      fwd_tile_pf<true>(h1c, ldh, 0, H, P2 + nd.t[2].off, P2 + nd.t[3].off, H, nullptr, 0, h2c, ldh, wave, pf);
+      pf_load_t(pft, P2 + nd.t[2].off, H, wave);
+    }
+    const float w3h2 = P2[nd.t[4].off + tid % H];
+    __syncthreads();
+    if (wave == 0) {
+      head_mfma<H / 4>(h2c, ldh, H, P2 + nd.t[4].off, P2 + nd.t[5].off, 1, qv, 8);
+      wave_sync();
+      double s_l = 0.0;
+      float g = 0.f;
+      if (lane < nvalid) {
+        const float diff = qv[lane * 8] - ys[lane];
+        g = (2.0f * diff) * a.inv_b;
+        s_l = (double)diff * (double)diff;
+      }
+      if (lane < MDP_R) dq[lane] = g;
+      s_l = sum16(s_l);
+      if (lane == 0) {  // [1..3] as critic 1's record (this lane wrote it)
+        const double* s1 = a.slab_stat + (int64_t)blk * 8;
+        double* st = a.slab_stat2 + (int64_t)blk * 8;
+        st[0] = s_l;
+        st[1] = s1[1];
+        st[2] = s1[2];
+        st[3] = s1[3];
+      }
+    }
+    __syncthreads();
+    critic_backward<H>(P2, nd, a.slab2 + (int64_t)blk * a.slab_stride - nd.off, dq, h1c, h2c, hA, hB, Xc, ldX, ag.cin,
+                       w3h2, pft, tid, wave, nw);
   }
-  if (tid == H) {
-    float s = 0.f;
-    for (int r = 0; r < MDP_R; ++r) s += dq[r];
-    slab[nd.t[5].off] = s;
-  }
-  for (int r = tid / H, h = tid % H; r < MDP_R; r += MDP_GEN_THREADS / H)
-    d2[r * ldh + h] = h2c[r * ldh + h] > 0.f ? dq[r] * w3h : 0.f;
-  __syncthreads();
-  MDP_STAMP(4);
-  // dh1 tiles then dW2 tiles, dealt over all waves
-  for (int t = wave; t < NT + NT * NT; t += nw) {
-    if (t < NT) dgrad_tile_relu_pf(d2, ldh, H, a.theta + nd.t[2].off, h1c, ldh, d1, ldh, t, pft);
-    else wgrad_tile(h1c, ldh, H, d2, ldh, H, slab + nd.t[2].off, t - NT);
-  }
-  colsum16(d2, ldh, H, slab + nd.t[3].off);
-  __syncthreads();
-  wgrad_waves(Xc, ldX, ag.cin, d1, ldh, H, slab + nd.t[0].off, 0, nw);
-  colsum16(d1, ldh, H, slab + nd.t[1].off);
   MDP_STAMP(5);
 }
 
 // PER: the prioritized-replay twin (A = CriticArgsPer), strict mode only
-template <int H, bool PER = false, class A = CriticArgs>
+// TWIN: the MATD3 twin (A = CriticArgsTwin), strict mode only
+template <int H, bool PER = false, class A = CriticArgs, bool TWIN = false>
 __global__ __launch_bounds__(MDP_GEN_THREADS) void k_critic_grad(A a) {
-  critic_body<H, PER>(a, a.topo, blockIdx.x);
+  critic_body<H, PER, A, TWIN>(a, a.topo, blockIdx.x);
 }
 
 // AA: ActorArgs, or the Topo-less ActorArgsHead of a gradient-pair launch
@@ -957,6 +1048,19 @@ hipError_t launch_critic_per(const CriticArgsPer& a, int lds, hipStream_t s) {
   return hipGetLastError();
 }
 template <int H>
+hipError_t launch_critic_twin(const CriticArgsTwin& a, int lds, hipStream_t s) {
+  static bool attr = false;
+  if (!attr) {
+    (void)hipFuncSetAttribute((const void*)k_critic_grad<H, false, CriticArgsTwin, true>,
+                              hipFuncAttributeMaxDynamicSharedMemorySize, MDP_LDS_BUDGET);
+    (void)hipGetLastError();
+    attr = true;
+  }
+  mdp_launch(k_critic_grad<H, false, CriticArgsTwin, true>, dim3((a.B + MDP_R - 1) / MDP_R), dim3(MDP_GEN_THREADS), lds,
+             s, a);
+  return hipGetLastError();
+}
+template <int H>
 hipError_t launch_actor(const ActorArgs& a, int lds, hipStream_t s) {
   static bool attr = false;
   if (!attr) {
@@ -1005,6 +1109,14 @@ hipError_t mdp_launch_critic_grad_per(const CriticArgsPer& a, int H, int lds_byt
     case 64: return launch_critic_per<64>(a, lds_bytes, s);
     case 128: return launch_critic_per<128>(a, lds_bytes, s);
     case 256: return launch_critic_per<256>(a, lds_bytes, s);
+    default: return hipErrorInvalidValue;
+  }
+}
+hipError_t mdp_launch_critic_grad_twin(const CriticArgsTwin& a, int H, int lds_bytes, hipStream_t s) {
+  switch (H) {
+    case 64: return launch_critic_twin<64>(a, lds_bytes, s);
+    case 128: return launch_critic_twin<128>(a, lds_bytes, s);
+    case 256: return launch_critic_twin<256>(a, lds_bytes, s);
     default: return hipErrorInvalidValue;
   }
 }

@@ -64,6 +64,18 @@ struct CriticArgsPer : CriticArgs {
   float* td_out;
 };
 
+// MATD3 (strict mode, general kernels): the argument block of the critic
+// kernel's twin instantiation.  theta2 / target2 are param-space bases of the
+// second critic and its target (the NDesc offsets of the arena's), slab2 /
+// slab_stat2 its partials [nwg][slab_stride] and records [nwg][8]; all four in
+// the caller's TD3 buffer.  The TD target is r + gamma (1 - done) min(q1', q2')
+struct CriticArgsTwin : CriticArgs {
+  const float* theta2;
+  const float* target2;
+  float* slab2;
+  double* slab_stat2;
+};
+
 // precomputed critic-step work of one batch row (k_actor_grad_r's extra
 // workgroups -> k_critic_grad_r in critic_post mode):
 //   h1 [64] | h2 [64] (critic forward) | target-critic L1 accumulator [64] | q | pad 3 | a~ [16]
@@ -375,6 +387,8 @@ inline int lds_critic_bytes(const Topo& t, int G) {
   return 4 * (mdp_r4(R * ldr) + 2 * mdp_r4(R * ldc) + 2 * mdp_r4((G + 1) * S) + mdp_r4((G + 1) * R * 8) +
               mdp_r4(R) + mdp_r4(MDP_MAX_AGENTS + 4));
 }
+// the twin instantiation keeps the rows' fp32 TD target for critic 2's loss seed
+inline int lds_critic_twin_bytes(const Topo& t, int G) { return lds_critic_bytes(t, G) + 4 * mdp_r4(16); }
 inline int lds_actor_bytes(const Topo& t) {
   const int R = 16, ldr = mdp_ld(t.row_stride), ldc = mdp_ld(t.cin_max), S = R * (t.H + 1);
   return 4 * (mdp_r4(R * ldr) + mdp_r4(R * ldc) + 6 * mdp_r4(S) + 5 * mdp_r4(R * 8) + mdp_r4(5 * t.H));
@@ -447,6 +461,7 @@ hipError_t mdp_launch_actor_grad(const ActorArgs& a, int H, int lds_bytes, hipSt
 hipError_t mdp_launch_grad_pair(const GradPairArgs& a, int H, int lds_bytes, hipStream_t s);
 hipError_t mdp_launch_critic_grad_r(const CriticArgs& a, int lds_bytes, hipStream_t s);
 hipError_t mdp_launch_critic_grad_per(const CriticArgsPer& a, int H, int lds_bytes, hipStream_t s);
+hipError_t mdp_launch_critic_grad_twin(const CriticArgsTwin& a, int H, int lds_bytes, hipStream_t s);
 hipError_t mdp_launch_critic_grad_r_per(const CriticArgsPer& a, int lds_bytes, hipStream_t s);
 hipError_t mdp_launch_actor_grad_r(const ActorArgs& a, int lds_bytes, hipStream_t s);
 hipError_t mdp_launch_rollout(const RolloutArgs& a, int H, int lds_bytes, hipStream_t s);

@@ -62,8 +62,11 @@ class Engine:
                  gamma=0.95, tau=1e-2, grad_clip=0.5, actor_reg=1e-3, adam_b1=0.9, adam_b2=0.999,
                  adam_eps=1e-8, seed=0, world_size=1, rank=0, device=None, episode_log_rows=0,
                  prioritized=False, per_alpha=0.6, per_beta0=0.4, per_beta_inc=0.001, per_eps=0.01,
-                 per_abs_err_upper=1.0, act_dims=None):
-        """act_dims: per-agent action widths A_i in 1..5 (Discrete(A_i)); None: 5 for
+                 per_abs_err_upper=1.0, act_dims=None, td3=False, policy_delay=2):
+        """td3: MATD3 (mdp_td3_enable) -- twin critics, the TD target from the smaller
+        target critic, the actor and the targets updated every policy_delay-th
+        critic step (1..8); strict mode, one GPU, no prioritized replay.
+        act_dims: per-agent action widths A_i in 1..5 (Discrete(A_i)); None: 5 for
         every agent, or the scenario's own.  The device keeps every action slot 5
         wide with zero pad entries; this class pads and slices at its boundary."""
         self.lib = _lib.load()
@@ -154,8 +157,16 @@ class Engine:
                 self._tensors[(i, net)] = infos
         self.prioritized = bool(prioritized)
         self.per_buf = None
+        self.td3 = bool(td3)
+        self.policy_delay = int(policy_delay)
+        self.td3_buf = None
+        if self.prioritized and self.td3:
+            self.close()
+            raise _lib.MdpError("td3 and prioritized replay do not combine (mdp_td3_enable)")
         if self.prioritized:
             self._per_enable(per_alpha, per_beta0, per_beta_inc, per_eps, per_abs_err_upper)
+        if self.td3:
+            self._td3_enable(self.policy_delay)
 
     # ------------------------------------------------------------ plumbing
     def _c(self, name, *args):
@@ -253,7 +264,10 @@ class Engine:
     def get_grads(self, agent):
         """{'actor': .., 'critic': ..}: the reduced gradients of agent's last update
         (logical shapes, as get_params)"""
-        return {"actor": self.get_params(agent, "g_actor"), "critic": self.get_params(agent, "g_critic")}
+        out = {"actor": self.get_params(agent, "g_actor"), "critic": self.get_params(agent, "g_critic")}
+        if self.td3:
+            out["critic2"] = self.get_params(agent, "g_critic2")
+        return out
 
     # ---------------------------------------------------------- parameters
     def _flat_shapes(self, agent, which):
@@ -298,35 +312,51 @@ class Engine:
 
     def init_params(self, seed=0):
         """tf.contrib.layers xavier_initializer (uniform) for all four nets per
-        agent, each drawn independently (targets are NOT copies: maddpg.py:66,104)."""
+        agent, each drawn independently (targets are NOT copies: maddpg.py:66,104).
+        A TD3 engine draws every agent's second critic and its target after all
+        of those, from the same generator: the four nets' values for a seed are
+        the same with and without td3."""
         rng = np.random.default_rng(seed)
         H = self.num_units
+
+        def draw(i, which):
+            shapes = self._flat_shapes(i, which)
+            p = {}
+            for k, (r, c) in zip(TENSOR_NAMES, shapes):
+                if k.startswith("W"):
+                    lim = np.sqrt(6.0 / (r + c))
+                    p[k] = rng.uniform(-lim, lim, size=(r, c)).astype(np.float32)
+                else:
+                    p[k] = np.zeros((r, c), np.float32)
+            self.set_params(i, which, p)
+
         for i in range(self.n):
             for which in ("actor", "critic", "tgt_actor", "tgt_critic"):
-                shapes = self._flat_shapes(i, which)
-                p = {}
-                for k, (r, c) in zip(TENSOR_NAMES, shapes):
-                    if k.startswith("W"):
-                        lim = np.sqrt(6.0 / (r + c))
-                        p[k] = rng.uniform(-lim, lim, size=(r, c)).astype(np.float32)
-                    else:
-                        p[k] = np.zeros((r, c), np.float32)
-                self.set_params(i, which, p)
+                draw(i, which)
+        if self.td3:
+            for i in range(self.n):
+                for which in ("critic2", "tgt_critic2"):
+                    draw(i, which)
         return H
 
     # --------------------------------------------------------- checkpoint
     SETS = ("actor", "critic", "tgt_actor", "tgt_critic", "m_actor", "v_actor", "m_critic", "v_critic")
+    TD3_SETS = ("critic2", "tgt_critic2", "m_critic2", "v_critic2")
 
     def state_dict(self):
         """Every variable tf.train.Saver would save (tf_util.py:259-273): weights,
-        targets, Adam slots and beta powers, keyed like the TF1 scopes."""
+        targets, Adam slots and beta powers, keyed like the TF1 scopes.  A TD3
+        engine adds the second critic's sets (TD3_SETS) and its beta powers; the
+        per-agent update counters are not part of it (they restart at 0)."""
         out = {}
         for i in range(self.n):
-            for w in self.SETS:
+            for w in self.SETS + (self.TD3_SETS if self.td3 else ()):
                 for k, v in self.get_params(i, w).items():
                     out[f"agent_{i}/{w}/{k}"] = v
             out[f"agent_{i}/actor/beta_power"] = self.get_beta_powers(i, 0)
             out[f"agent_{i}/critic/beta_power"] = self.get_beta_powers(i, 1)
+            if self.td3:
+                out[f"agent_{i}/critic2/beta_power"] = self.get_beta_powers(i, 2)
         return out
 
     def load_state_dict(self, sd, agents=None):
@@ -338,6 +368,13 @@ class Engine:
                 self.set_params(i, w, {k: sd[f"agent_{i}/{w}/{k}"] for k in TENSOR_NAMES})
             self.set_beta_powers(i, 0, sd[f"agent_{i}/actor/beta_power"])
             self.set_beta_powers(i, 1, sd[f"agent_{i}/critic/beta_power"])
+            # the second critic's sets: restored when the engine has them and the
+            # checkpoint holds them (a MADDPG checkpoint leaves the twin as it is;
+            # a non-TD3 engine ignores the keys)
+            if self.td3 and f"agent_{i}/critic2/beta_power" in sd:
+                for w in self.TD3_SETS:
+                    self.set_params(i, w, {k: sd[f"agent_{i}/{w}/{k}"] for k in TENSOR_NAMES})
+                self.set_beta_powers(i, 2, sd[f"agent_{i}/critic2/beta_power"])
 
     @staticmethod
     def checkpoint_path(fname):
@@ -353,6 +390,9 @@ class Engine:
         tf.train.Saver().save(sess, fname) writes it (tf_util.py:267-273;
         `fname`.index + `fname`.data-00000-of-00001 + the `checkpoint` state
         file; no .meta -- the graph is built by code on both sides)."""
+        if fmt == "tf1" and self.td3:
+            raise ValueError("save_state(fmt='tf1') on a TD3 engine: the second critic has no reference variable "
+                             "names; save as npz")
         if fmt == "tf1":
             from .common import tf_checkpoint as tfc
             self._drop_stale(fname, keep="tf1")
@@ -465,6 +505,40 @@ class Engine:
             self.close()
             raise
         self.per_nodes = int(self.lib.mdp_per_tree_nodes(self.h))
+
+    # --------------------------------------------------------------- MATD3
+    def _td3_enable(self, policy_delay):
+        """twin critics + delayed policy updates (mdp_td3_enable): the second
+        critic's state in a second device buffer; before the first update / train call"""
+        nbytes = self.lib.mdp_td3_bytes(ctypes.byref(self.cfg))
+        if nbytes < 0:
+            raise ValueError("mdp_td3_bytes refused the configuration")
+        with torch.cuda.device(self.device):
+            self.td3_buf = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        try:
+            self._c("mdp_td3_enable", self._ptr(self.td3_buf), nbytes, int(policy_delay))
+        except _lib.MdpError:
+            self.td3_buf = None
+            self.close()
+            raise
+
+    TD3_REGIONS = ("theta2", "target2", "adam_m2", "adam_v2", "grad2")
+
+    def td3_region(self, name):
+        """float32 view of one of the second critic's param-space regions in the TD3
+        buffer (the arena regions' offsets: mdp_tensor(agent, 1, t).offset)"""
+        if not self.td3:
+            raise _lib.MdpError("td3_region: MATD3 is not enabled")
+        stride = (4 * self.param_floats + 255) // 256 * 256
+        k = self.TD3_REGIONS.index(name)
+        return self.td3_buf[k * stride: k * stride + 4 * self.param_floats].view(torch.float32)
+
+    def td3_info(self, agent):
+        """{critic_updates, actor_updates, q_loss, q_loss2} of agent's last update (mdp_td3_info)"""
+        out = (ctypes.c_double * 4)()
+        self._c("mdp_td3_info", int(agent), out)
+        return {"critic_updates": int(out[0]), "actor_updates": int(out[1]), "q_loss": np.float32(out[2]),
+                "q_loss2": np.float32(out[3])}
 
     def per_sample(self, agent, count, u=None):
         """(positions int32 [count], IS weights float32 [count]) from agent's tree:

@@ -13,6 +13,13 @@ the reference does: a ``list`` of numpy scalars with its dtypes (``q_loss``,
 ``engine.UPDATE_STAT_DTYPES``), read after the update (the reference's
 ``session.run`` is synchronous too).
 
+With ``args.td3`` (``--td3``, ``args.policy_delay`` default 2) the session's
+engine is a MATD3 one (``DESIGN.md`` section 17): ``update`` runs the twin critic step
+and, every ``policy_delay``-th time, the actor step and the Polyak updates; the
+returned list keeps its dtypes, with ``q_loss`` critic 1's, ``p_loss`` that of
+this agent's most recent actor step (0 before the first) and
+``mean(target_q_next)`` the mean of the smaller target Q.
+
 ``model`` must be the reference's ``mlp_model`` (``train.py:39-46``: two
 hidden ReLU layers of ``args.num_units`` and a linear output, TF
 ``fully_connected`` with Xavier-uniform weights) -- the architecture the HIP

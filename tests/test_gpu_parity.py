@@ -191,10 +191,19 @@ def _clip_mode_distance(eng, c, i, dgs):
         n64 = {k: float(nets.tensor_norm(v, "fp64")) for k, v in g.items()}
         n32 = {k: float(nets.tensor_norm(v, "fp32")) for k, v in g.items()}
         out[(w, "norm_rel_gap")] = max(abs(n32[k] - n64[k]) / max(n64[k], 1e-30) for k in g)
+        out[(w, "clip_active")] = {k: n64[k] > 0.5 for k in g}
         for mode in ("fp64", "fp32"):
             p = {k: np.asarray(v, np.float32).reshape(dev[k].shape).copy() for k, v in c["params"][i][w].items()}
-            nets.Adam(p).apply(p, {k: nets.clip_by_norm(v, 0.5, mode) for k, v in g.items()})
+            opt = nets.Adam(p)
+            opt.apply(p, {k: nets.clip_by_norm(v, 0.5, mode) for k, v in g.items()})
             out[(w, mode)] = max(float(np.abs(dev[k] - p[k]).max()) for k in p)
+            if mode == "fp64":
+                # the step's own m and v (at t = 1: gc c1 and gc^2 c2, so they carry the clip
+                # factor that theta barely sees), in fp32 spacings of the fp64-norm step's value
+                for slot, ref in (("m", opt.m), ("v", opt.v)):
+                    d = eng.get_params(i, f"{slot}_{w}")
+                    out[(w, f"{slot}_ulps")] = max(
+                        float((np.abs(d[k].astype(np.float64) - ref[k]) / np.spacing(np.abs(ref[k]))).max()) for k in ref)
     return out
 
 
@@ -239,6 +248,12 @@ def _update_parity(dims, B, L, seed, local_q=None, H=64, check_round=True, devic
         for w in ("critic", "actor"):
             # the device's step IS the fp64-norm clip applied to its own gradient
             assert cm[(w, "fp64")] < 1e-6, (i, w, cm)
+            # ... and so are its m and v.  The two fp64 sums of squares (numpy's order, the
+            # device's) can round to neighbouring fp32 norms: one spacing of the norm is
+            # 1.2e-7 relative, gc = (g clip) / denom adds a rounding (1.8e-7), m = gc c1 another
+            # (2.4e-7: 4 spacings of m), v = gc gc c2 twice gc's error and two roundings
+            # (4.8e-7: 8 spacings of v)
+            assert cm[(w, "m_ulps")] <= 4 and cm[(w, "v_ulps")] <= 8, (i, w, cm)
         for net, name in ((1, "grad_critic"), (0, "grad_actor")):
             dg = dgs[net]
             for k, ref in og[name].items():
@@ -284,6 +299,10 @@ def _update_parity(dims, B, L, seed, local_q=None, H=64, check_round=True, devic
               f"{max(r[(w, 'fp64')] for r in creport):.3e}, vs fp32-norm (TF1 reduce_sum) step "
               f"{max(r[(w, 'fp32')] for r in creport):.3e}; |norm32 - norm64| / norm64 <= "
               f"{max(r[(w, 'norm_rel_gap')] for r in creport):.3e}")
+        print(f"   {w}: m, v vs the fp64-norm step, worst fp32 spacings: m {max(r[(w, 'm_ulps')] for r in creport):.2f}, "
+              f"v {max(r[(w, 'v_ulps')] for r in creport):.2f}; clip active per agent: "
+              + "; ".join(" ".join(f"{k}:{'on' if on else 'off'}" for k, on in r[(w, 'clip_active')].items())
+                          for r in creport))
     if after is not None:
         after(eng)
     return worst

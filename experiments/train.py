@@ -9,6 +9,7 @@ this is exactly the reference loop).  Extra flags: ``--num-envs``, ``--seed``,
 ``--num-agents``/``--scenario-adversaries`` (scenario size), ``--train-every``,
 ``--evaluate`` / ``--eval-episodes`` / ``--eval-mode`` / ``--adv-load-dir``
 (device-side policy evaluation on fixed episode ids; it leaves training untouched),
+``--eval-q`` (with either: the critics' Q against the realised discounted return),
 ``--evaluate --tournament DIR [DIR ...]`` / ``--tournament-team`` (the cross-play
 table of several checkpoints in one launch).
 
@@ -111,6 +112,10 @@ def parse_args(argv=None):
     parser.add_argument("--eval-mode", choices=["sample", "mean"], default="sample",
                         help="sample: the policies act as in training (Gumbel-softmax); mean: softmax of the "
                              "logits without noise")
+    parser.add_argument("--eval-q", action="store_true", default=False,
+                        help="--evaluate, or training with --eval-episodes: also score the critics -- Q against the "
+                             "discounted return the policies then collect on the same ids (mean and RMS gap per "
+                             "agent and critic)")
     parser.add_argument("--adv-load-dir", type=str, default="",
                         help="--evaluate: take the first --num-adversaries agents from this checkpoint and the rest "
                              "from --load-dir (cross-play)")
@@ -225,6 +230,21 @@ def scenario_has_records(sp):
     return sp.name not in ("simple", "simple_speaker_listener")
 
 
+def eval_q_summary(res):
+    """what --eval-q keeps of Engine.evaluate_q: the summary, the window and the per-episode gaps"""
+    return {"steps": res["steps"], "scored": res["scored"], "episodes": int(res["gap"].shape[0]),
+            "gap": res["gap"].cpu().numpy(), **res["summary"]}
+
+
+def eval_q_lines(s):
+    """one line per agent: per critic the mean Q and mean return-to-go over the
+    scored steps, the mean gap and its RMS over the episodes"""
+    for i in range(len(s["q_mean"])):
+        yield ("eval_q agent {}: mean Q {}, mean return-to-go {}, mean gap {}, rms gap {} ({} of {} steps scored, "
+               "truncation {:.4f})".format(i, s["q_mean"][i], s["g_mean"][i][0], s["gap_mean"][i], s["gap_rms"][i],
+                                           s["scored"], s["steps"], s["truncation"]))
+
+
 def evaluate(arglist, runner, exp_name, rank):
     """--evaluate: the loaded policies play evaluation episodes [0, M) on the
     device (Engine.evaluate), M = --eval-episodes or 1024.  Prints every agent's
@@ -248,6 +268,10 @@ def evaluate(arglist, runner, exp_name, rank):
             out["bench_mean"] = mean_rec
             for i in range(n):
                 print("eval agent {}: mean record sums per episode {}".format(i, mean_rec[i].tolist()), flush=True)
+        if arglist.eval_q:
+            out["eval_q"] = eval_q_summary(runner.evaluate_q(M, first_episode=0, mode=arglist.eval_mode))
+            for line in eval_q_lines(out["eval_q"]):
+                print(line, flush=True)
         file_name = arglist.benchmark_dir + exp_name + '_eval.pkl'
         os.makedirs(os.path.dirname(file_name) or ".", exist_ok=True)
         with open(file_name, 'wb') as fp:
@@ -433,6 +457,7 @@ def _train(arglist, runner, exp_name, world, rank):
     E, L = arglist.num_envs, arglist.max_episode_len
     curve = LearningCurve(arglist.save_rate, arglist.num_episodes, n)
     eval_curve = []      # --eval-episodes: per curve point, every agent's mean return on the fixed ids
+    eval_q_curve = []    # --eval-q: per curve point, the critics' summary on the same ids
     t_start = time.time()
     t_run = time.perf_counter()
     vec_steps = 0
@@ -473,12 +498,23 @@ def _train(arglist, runner, exp_name, world, rank):
                 eval_curve.append(ev["mean"])
                 print("eval: episodes: {}, eval episodes: {}, mean return: {}, std: {}".format(
                     length, arglist.eval_episodes, ev["mean"], ev["std"]), flush=True)
+            if arglist.eval_q and points:
+                eq = eval_q_summary(runner.evaluate_q(arglist.eval_episodes, first_episode=0, mode=arglist.eval_mode))
+                del eq["gap"]
+                for length, _, _ in points:
+                    eval_q_curve.append(dict(eq, train_episodes=length))
+                    print("eval_q: episodes: {}, eval episodes: {}, mean Q: {}, mean return-to-go: {}, mean gap: {}, "
+                          "rms gap: {}".format(length, arglist.eval_episodes, eq["q_mean"],
+                                               [g[0] for g in eq["g_mean"]], eq["gap_mean"], eq["gap_rms"]), flush=True)
         if curve.done:
             if rank == 0:
                 os.makedirs(arglist.plots_dir, exist_ok=True)
                 if arglist.eval_episodes > 0:
                     with open(arglist.plots_dir + exp_name + '_eval_rewards.pkl', 'wb') as fp:
                         pickle.dump(eval_curve, fp)
+                    if arglist.eval_q:
+                        with open(arglist.plots_dir + exp_name + '_eval_q.pkl', 'wb') as fp:
+                            pickle.dump(eval_q_curve, fp)
                 with open(arglist.plots_dir + exp_name + '_rewards.pkl', 'wb') as fp:
                     pickle.dump(curve.final_ep_rewards, fp)
                 with open(arglist.plots_dir + exp_name + '_agrewards.pkl', 'wb') as fp:

@@ -388,6 +388,49 @@ int mdp_env_step_bench_u(mdp_handle* h, float* info_dev, const float* u_dev);
 enum { MDP_EVAL_SAMPLE = 0, MDP_EVAL_MEAN = 1 };
 int mdp_evaluate(mdp_handle* h, int64_t first_episode, int32_t episodes, int32_t mode,
                  const float* u_dev, float* ret_dev, float* bench_dev);
+/* ---- critic evaluation: Q against the realised return, in the same launch --
+ * Plays mdp_evaluate's episode ids and scores the handle's live (non-target)
+ * critics on them: Q_j(o_t, a_t) beside the discounted return the policies then
+ * collect -- the overestimation diagnostic (TD3's first figure).  The reference
+ * never stores done = 1 for these scenarios (`terminal` only resets the env), so
+ * a critic estimates the return of the CONTINUING world: the episode plays a
+ * caller-chosen number of steps without reset, and only its leading part is scored.
+ *   episode   id g is mdp_evaluate's id: reset stream 0x60000, noise stream
+ *             0x70000 | agent with counter t and row g, the same modes, the same
+ *             actor forward path.  It plays `steps` steps, 1 <= steps <= 4096,
+ *             with no reset and without regard to max_episode_len: for
+ *             t < max_episode_len the trajectory is mdp_evaluate's bit for bit,
+ *             and a run with more steps reproduces a run with fewer on the
+ *             common prefix
+ *   C         critics per agent: 1, or 2 after mdp_td3_enable
+ *   q         [i][t][j][C] Q_j (then Q2_j, of the TD3 buffer's MDP_CRITIC2) on the
+ *             joint [obs_n | act_n] of step t ([obs_j | act_j] for a local_q
+ *             agent), after every agent's action of step t and before World.step;
+ *             the value mdp_q_values(j, 0, ...) gives on that row, bit for bit
+ *   rew       [i][t][j] the step rewards, the values mdp_evaluate's ret sums
+ *   g         [i][t][j] the return-to-go in fp64 from cfg.gamma (fp32): G_steps = 0,
+ *             G_t = (double)r_t + (double)gamma * G_{t+1}, stored as (float)G_t
+ *   gap       [i][j][C] (float)((1 / scored) * sum_{t < scored} ((double)q_t - G_t)),
+ *             the sum in fp64 in step order, 1 <= scored <= steps
+ * Truncation: G_t lacks the rewards from step `steps` on, i.e. gamma^(steps - t)
+ * times a return-to-go; over the scored steps that is at most a factor
+ * gamma^(steps - scored + 1) of the return's scale (0.0094 at gamma 0.95,
+ * steps - scored = 90).  Nothing is bootstrapped from Q_steps.
+ * u_dev: NULL or [episodes][steps][n_agents][5] uniforms (SAMPLE only).
+ * Two launches on the handle's stream (the episodes, then one thread per
+ * (episode, agent) for g and gap), both timed as MDP_K_EVAL; no synchronisation.
+ * It neither reads nor writes the training env state, the replay ring, the
+ * episode log, the comm state, any control field (env step / episode counters,
+ * tickets, the index RNG, the noise counter), the prioritized-replay buffer or
+ * the TD3 counters; of the parameters it reads the actors and the live critics.
+ * Refused with a message that names the entry point and the argument, before any
+ * launch: a handle without a device env, a bad mode, count, id range, steps or
+ * scored, u_dev with MDP_EVAL_MEAN, a NULL q_dev / rew_dev / g_dev / gap_dev, any
+ * of the five pointers that is not device memory of the full size, a stream
+ * that is capturing a graph.  The handle trains and evaluates on after a refusal. */
+int mdp_evaluate_q(mdp_handle* h, int64_t first_episode, int32_t episodes, int32_t mode,
+                   int32_t steps, int32_t scored, const float* u_dev,
+                   float* q_dev, float* rew_dev, float* g_dev, float* gap_dev);
 /* the start states of those ids: pos/vel [episodes][n_entities][2], goal [episodes]
  * (host, synchronises; staged through a temporary device buffer freed before return) */
 int mdp_eval_initial_state(mdp_handle* h, int64_t first_episode, int32_t episodes,
@@ -555,7 +598,7 @@ enum mdp_kernel_kind {
     MDP_K_APPLY = 4, MDP_K_ROLLOUT = 5, MDP_K_REDUCE = 6, MDP_K_REDUCE_APPLY = 7,
     MDP_K_ALLREDUCE = 8,   /* the RCCL data-parallel all-reduces (not a kernel of this library) */
     MDP_K_PER_SYNC = 9, MDP_K_PER_SAMPLE = 10, MDP_K_PER_UPDATE = 11,   /* prioritized replay (mdp_per.hip) */
-    MDP_K_EVAL = 12,       /* k_eval_episodes (mdp_evaluate, mdp_evaluate_matchups) */
+    MDP_K_EVAL = 12,       /* k_eval_episodes (mdp_evaluate, mdp_evaluate_matchups, mdp_evaluate_q + its k_eval_returns) */
     MDP_K_COUNT = 13
 };
 int mdp_prof_enable(mdp_handle* h, int32_t kind, int32_t on);

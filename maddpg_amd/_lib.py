@@ -36,12 +36,13 @@ KERNEL = {"index": 0, "gather": 1, "critic_grad": 2, "actor_grad": 3, "apply": 4
           "reduce": 6, "reduce_apply": 7, "allreduce": 8}
 # the prioritized-replay kernels (mdp_per.hip), timed only when asked for by name
 KERNEL_PER = {"per_sync": 9, "per_sample": 10, "per_update": 11}
-# the policy-evaluation kernel (k_eval_episodes: mdp_evaluate and mdp_evaluate_matchups), timed only
-# when asked for by name
+# the policy-evaluation kernels (k_eval_episodes: mdp_evaluate, mdp_evaluate_matchups and mdp_evaluate_q,
+# whose k_eval_returns launch counts here too), timed only when asked for by name
 KERNEL_EVAL = {"eval": 12}
 EVAL_MODE = {"sample": 0, "mean": 1}   # MDP_EVAL_SAMPLE / MDP_EVAL_MEAN
 EVAL_MAX_EPISODES = 1 << 20            # ids per mdp_evaluate call
-EVAL_MAX_SETS = 4096                   # sets of a bank / matchups per mdp_evaluate_matchups call
+EVAL_Q_MAX_STEPS = 4096                # steps per mdp_evaluate_q episode
+EVAL_MAX_SETS = 4096                  # sets of a bank / matchups per mdp_evaluate_matchups call
 EVAL_MAX_MATCHUP_EPISODES = 1 << 22    # matchups x episodes per mdp_evaluate_matchups call
 
 
@@ -153,6 +154,7 @@ SIGNATURES = {
     "mdp_env_step_bench": (ctypes.c_int, [_P, _P]),
     "mdp_env_step_bench_u": (ctypes.c_int, [_P, _P, _P]),
     "mdp_evaluate": (ctypes.c_int, [_P, _I64, _I32, _I32, _P, _P, _P]),
+    "mdp_evaluate_q": (ctypes.c_int, [_P, _I64, _I32, _I32, _I32, _I32, _P, _P, _P, _P, _P]),
     "mdp_eval_initial_state": (ctypes.c_int, [_P, _I64, _I32, _F32P, _F32P, _I32P]),
     "mdp_actor_set_floats": (_I64, [_P]),
     "mdp_actor_set_write": (ctypes.c_int, [_P, _P, _I32, _F32P, _I64]),

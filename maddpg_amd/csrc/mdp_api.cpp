@@ -2839,6 +2839,75 @@ int mdp_evaluate(mdp_handle* h, int64_t first_episode, int32_t episodes, int32_t
   return 0;
 }
 
+// ---- critic evaluation (k_eval_episodes<H, EvalQArgs>, then k_eval_returns)
+#define MDP_EVAL_Q_MAX_STEPS 4096
+int mdp_evaluate_q(mdp_handle* h, int64_t first_episode, int32_t episodes, int32_t mode, int32_t steps, int32_t scored,
+                   const float* u_dev, float* q_dev, float* rew_dev, float* g_dev, float* gap_dev) {
+  if (need_env(h)) return -1;
+  const char* fn = "mdp_evaluate_q";
+  if (mode != MDP_EVAL_SAMPLE && mode != MDP_EVAL_MEAN)
+    return fail(h, "mdp_evaluate_q: mode must be MDP_EVAL_SAMPLE (0) or MDP_EVAL_MEAN (1)");
+  if (eval_range_ok(h, fn, first_episode, episodes)) return -1;
+  if (steps < 1 || steps > MDP_EVAL_Q_MAX_STEPS) return fail(h, "mdp_evaluate_q: 1 <= steps <= 4096");
+  if (scored < 1 || scored > steps) return fail(h, "mdp_evaluate_q: 1 <= scored <= steps");
+  if (u_dev && mode == MDP_EVAL_MEAN) return fail(h, "mdp_evaluate_q: u_dev is given but MDP_EVAL_MEAN draws no noise");
+  if (!q_dev) return fail(h, "mdp_evaluate_q: q_dev is null");
+  if (!rew_dev) return fail(h, "mdp_evaluate_q: rew_dev is null");
+  if (!g_dev) return fail(h, "mdp_evaluate_q: g_dev is null");
+  if (!gap_dev) return fail(h, "mdp_evaluate_q: gap_dev is null");
+  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+  if (h->capturing || (hipStreamIsCapturing(h->stream, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone))
+    return fail(h, "mdp_evaluate_q: the handle's stream is capturing a graph (evaluation is not captured)");
+  (void)hipGetLastError();
+  const int n = h->cfg.n_agents, C = h->td3 ? 2 : 1;
+  const int64_t en = 4 * (int64_t)episodes * n, ens = en * steps;
+  MDP_DEV(h, u_dev, ens * MDP_ACT_DIM, fn, true);
+  MDP_DEV(h, q_dev, ens * C, fn, false);
+  MDP_DEV(h, rew_dev, ens, fn, false);
+  MDP_DEV(h, g_dev, ens, fn, false);
+  MDP_DEV(h, gap_dev, en * C, fn, false);
+  const int lds = lds_eval_q_bytes(h->L.topo);
+  if (lds > MDP_LDS_BUDGET)
+    return fail(h, "mdp_evaluate_q: the configuration leaves no LDS for the DDPG critics' input tile");
+  EvalQArgs a;
+  a.topo = h->L.topo;
+  a.env = h->L.env;
+  a.theta = h->theta;
+  a.seed = h->cfg.seed;
+  a.first = (uint32_t)first_episode;
+  a.episodes = episodes;
+  a.mode = mode;
+  a.u_in = u_dev;
+  a.ret = nullptr;
+  a.bench = nullptr;
+  a.theta2 = h->td3 ? h->theta2 : nullptr;
+  a.steps = steps;
+  a.ncrit = C;
+  a.qin = lds_eval_q_in(h->L.topo);
+  a.q = q_dev;
+  a.rew = rew_dev;
+  EvalRetArgs r;
+  r.episodes = episodes;
+  r.n = n;
+  r.steps = steps;
+  r.scored = scored;
+  r.ncrit = C;
+  r.gamma = h->cfg.gamma;
+  r.q = q_dev;
+  r.rew = rew_dev;
+  r.g = g_dev;
+  r.gap = gap_dev;
+  {
+    ProfScope p(h, MDP_K_EVAL);
+    HIPCHK(h, mdp_launch_eval_q(a, h->L.topo.H, lds, h->stream));
+  }
+  {
+    ProfScope p(h, MDP_K_EVAL);
+    HIPCHK(h, mdp_launch_eval_returns(r, h->stream));
+  }
+  return 0;
+}
+
 int mdp_eval_initial_state(mdp_handle* h, int64_t first_episode, int32_t episodes, float* pos_host, float* vel_host,
                            int32_t* goal_host) {
   if (need_env(h)) return -1;

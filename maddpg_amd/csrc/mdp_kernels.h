@@ -361,6 +361,28 @@ struct EvalMuArgs : EvalEpArgs {
   int matchups;          // ret [matchups][episodes][n], bench [matchups][episodes][n][MDP_BENCH_W]
 };
 
+// k_eval_episodes<H, EvalQArgs> (mdp_evaluate_q): EvalEpArgs' episodes played
+// `steps` steps without reset, every agent's live critic(s) scored on the row
+// tile after the step's sample; ret / bench are unused (null)
+struct EvalQArgs : EvalEpArgs {
+  const float* theta2;  // the TD3 buffer's theta region (the twin critic), null when ncrit == 1
+  int steps;            // steps per episode; u_in is [episodes][steps][n][MDP_ACT_DIM]
+  int ncrit;            // C: 1, or 2 after mdp_td3_enable
+  int qin;              // widest critic input of a local_q agent (0: none): the staging tile's width
+  float* q;             // [episodes][steps][n][ncrit]
+  float* rew;           // [episodes][steps][n]
+};
+
+// k_eval_returns: one thread per (episode, agent) over the traces k_eval_episodes<H, EvalQArgs> wrote
+struct EvalRetArgs {
+  int episodes, n, steps, scored, ncrit;
+  float gamma;
+  const float* q;    // [episodes][steps][n][ncrit]
+  const float* rew;  // [episodes][steps][n]
+  float* g;          // [episodes][steps][n]
+  float* gap;        // [episodes][n][ncrit]
+};
+
 struct EvalArgs {
   const float* P;
   NDesc net;
@@ -430,6 +452,18 @@ inline int lds_rollout_bytes(const Topo& t) {
 }
 // k_eval_episodes<H, EvalMuArgs>: k_rollout's carve plus the matchup's table row
 inline int lds_eval_matchups_bytes(const Topo& t) { return lds_rollout_bytes(t) + 4 * mdp_r4(MDP_MAX_AGENTS); }
+// k_eval_episodes<H, EvalQArgs>: k_rollout's carve plus the [obs_j | act_j] staging
+// tile of the local_q agents' critics (qin: the widest such input, 0 when none)
+inline int lds_eval_q_in(const Topo& t) {
+  int qin = 0;
+  for (int j = 0; j < t.n; ++j)
+    if (t.ag[j].local_q && t.ag[j].cin > qin) qin = t.ag[j].cin;
+  return qin;
+}
+inline int lds_eval_q_bytes(const Topo& t) {
+  const int qin = lds_eval_q_in(t);
+  return lds_rollout_bytes(t) + (qin ? 4 * mdp_r4(16 * mdp_ld(qin)) : 0);
+}
 inline int lds_eval_bytes(int in, int H) {
   const int R = 16, ldx = mdp_ld(in), ldh = H + 1;
   return 4 * (mdp_r4(R * ldx) + 2 * mdp_r4(R * ldh) + mdp_r4(R * 8));
@@ -468,6 +502,8 @@ hipError_t mdp_launch_rollout(const RolloutArgs& a, int H, int lds_bytes, hipStr
 hipError_t mdp_launch_eval(const EvalArgs& a, int H, int lds_bytes, hipStream_t s);
 hipError_t mdp_launch_eval_episodes(const EvalEpArgs& a, int H, int lds_bytes, hipStream_t s);
 hipError_t mdp_launch_eval_matchups(const EvalMuArgs& a, int H, int lds_bytes, hipStream_t s);
+hipError_t mdp_launch_eval_q(const EvalQArgs& a, int H, int lds_bytes, hipStream_t s);
+hipError_t mdp_launch_eval_returns(const EvalRetArgs& a, hipStream_t s);
 hipError_t mdp_launch_eval_reset(const EnvDesc& env, uint64_t seed, uint32_t first, int count, float* pos, float* vel,
                                  int32_t* goal, hipStream_t s);
 hipError_t mdp_launch_apply(const ApplyArgs& a, hipStream_t s);

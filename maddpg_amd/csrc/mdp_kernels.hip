@@ -1136,9 +1136,20 @@ __global__ __launch_bounds__(MDP_NT) void k_rollout(RolloutArgs a) {
 // and writes ret / bench at [m][episode][agent]; ids, reset and noise streams
 // and the injected uniforms do not depend on m.  Everything else is the code
 // below, unchanged; the EvalEpArgs instantiations compile to what they were.
+//
+// Args = EvalQArgs (QV, mdp_evaluate_q): the episode plays a.steps steps (no
+// reset, max_ep_len is not looked at; u_in is strided by a.steps) and, once every
+// agent's action of step t is in the row tile and before the physics, each agent's
+// live critic -- then the TD3 twin -- is run on the tile with mlp_fwd_tile<H>, the
+// routine k_mlp_eval (mdp_q_values) runs, in h1 / h2 / lg, which are free there.
+// The MADDPG critic's input is the tile's [obs_n | act_n] prefix in place; a
+// local_q agent's [obs_j | act_j] is staged into a tile behind k_rollout's carve
+// (lds_eval_q_bytes).  q and the step rewards of the valid rows go to global
+// memory; ret / bench are not written.  k_eval_returns folds them afterwards.
 template <int H, class Args = EvalEpArgs>
 __global__ __launch_bounds__(MDP_NT) void k_eval_episodes(Args a) {
   constexpr bool MU = std::is_same<Args, EvalMuArgs>::value;
+  constexpr bool QV = std::is_same<Args, EvalQArgs>::value;
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const Topo& T = a.topo;
   const EnvDesc& E = a.env;
@@ -1158,6 +1169,13 @@ __global__ __launch_bounds__(MDP_NT) void k_eval_episodes(Args a) {
   int* sgoal = reinterpret_cast<int*>(cv.take(MDP_R));
   // MU: the matchup's table row (lds_eval_matchups_bytes adds it behind k_rollout's carve)
   int* stab = MU ? reinterpret_cast<int*>(cv.take(MDP_MAX_AGENTS)) : nullptr;
+  // QV: the local_q critics' input tile (lds_eval_q_bytes adds it behind k_rollout's carve)
+  int ldq = 0;
+  float* qx = nullptr;
+  if constexpr (QV) {
+    ldq = lds_ld(a.qin);
+    qx = a.qin ? cv.take(MDP_R * ldq) : nullptr;
+  }
   // this step's records of the tile, [R][n][MDP_BENCH_W]: in h1, which is free
   // between a step's forward and the next one's
   static_assert(MDP_R * MDP_MAX_AGENTS * MDP_BENCH_W <= MDP_R * (H + 1), "record tile fits h1");
@@ -1215,7 +1233,8 @@ __global__ __launch_bounds__(MDP_NT) void k_eval_episodes(Args a) {
   const int br = tid / n, bj = tid - br * n;
   __syncthreads();
 
-  const int nst = E.max_ep_len;
+  int nst = E.max_ep_len;
+  if constexpr (QV) nst = a.steps;
   for (int t = 0; t < nst; ++t) {
     // the sample of (row lane, agent j): k_rollout's, or the noise-free softmax
     auto sample = [&](const float* logits, int row, int j, float* dst) {
@@ -1297,11 +1316,36 @@ __global__ __launch_bounds__(MDP_NT) void k_eval_episodes(Args a) {
       __syncthreads();
     }
 
+    if constexpr (QV) {
+      // Q_j(o_t, a_t) of the live critic(s): every action of step t is in the tile
+      for (int j = 0; j < n; ++j) {
+        const ADesc& aj = T.ag[j];
+        const float* X = rowt;
+        int ldx = ldr;
+        if (aj.local_q) {
+          for (int q = tid; q < MDP_R * aj.cin; q += MDP_NT) {
+            const int r = q / aj.cin, c = q - r * aj.cin;
+            qx[r * ldq + c] = rowt[r * ldr + (c < aj.obs_dim ? aj.obs_off + c : aj.act_off + c - aj.obs_dim)];
+          }
+          __syncthreads();
+          X = qx;
+          ldx = ldq;
+        }
+        for (int c = 0; c < a.ncrit; ++c) {
+          mlp_fwd_tile<H>(X, ldx, aj.cin, c ? a.theta2 : a.theta, aj.critic, h1, h2, ldh, lg, 8);
+          if (tid < nvalid) a.q[(((int64_t)(i0 + tid) * nst + t) * n + j) * a.ncrit + c] = lg[tid * 8];
+        }
+      }
+    }
+
     env_physics_tile(E, sp, sv, rowt + T.ag[0].act_off, ldr, sfo, nvalid);
     if (tid < nvalid) {
       const float* p = sp + tid * 2 * MDP_MAX_ENT;
       float* rew = rowt + tid * ldr + T.ag[0].rew_off;  // rew_0 .. rew_{n-1} are contiguous (mdp_topo.h)
       env_reward(E, p, sgoal[tid], rew);
+      if constexpr (QV) {
+        for (int j = 0; j < n; ++j) a.rew[((int64_t)(i0 + tid) * nst + t) * n + j] = rew[j];
+      }
       if (a.bench) env_bench(E, p, sgoal[tid], rec + tid * n * MDP_BENCH_W);
       for (int j = 0; j < n; ++j) epr[tid * MDP_MAX_AGENTS + j] = epr[tid * MDP_MAX_AGENTS + j] + rew[j];
     }
@@ -1315,6 +1359,7 @@ __global__ __launch_bounds__(MDP_NT) void k_eval_episodes(Args a) {
     __syncthreads();
   }
 
+  if constexpr (QV) return;  // q / rew are written; the returns are k_eval_returns'
   if (tid < MDP_R * n && br < nvalid) {
     int64_t o = (int64_t)(i0 + br) * n + bj;
     if constexpr (MU) o += (int64_t)blockIdx.y * a.episodes * n;
@@ -1324,6 +1369,56 @@ __global__ __launch_bounds__(MDP_NT) void k_eval_episodes(Args a) {
       for (int k = 0; k < MDP_BENCH_W; ++k) a.bench[o * MDP_BENCH_W + k] = bsum[k];
     }
   }
+}
+
+// Return-to-go and critic gap of mdp_evaluate_q, one thread per (episode, agent),
+// in fp64 from the fp32 gamma: G_steps = 0, G_t = r_t + gamma G_{t+1}; g[t] =
+// (float)G_t; gap[c] = (float)((1 / scored) sum_{t < scored} (q_t[c] - G_t)), the
+// sum in step order.  The recursion runs backward and the sum forward: after the
+// pass that writes g, the scored steps are walked in blocks of EVR_B in step
+// order; for each block the recursion is run again from the end of the trace
+// (the same operations, so the same G_t), its last EVR_B values are kept in
+// registers (unrolled, constant indices: no scratch) and the block's terms are
+// added in step order.  Cost steps * (1 + scored / EVR_B) recursion steps.
+#define EVR_B 32
+__global__ __launch_bounds__(256) void k_eval_returns(EvalRetArgs a) {
+  const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (e >= (int64_t)a.episodes * a.n) return;
+  const int64_t ep = e / a.n;
+  const int j = (int)(e - ep * a.n);
+  const int n = a.n, steps = a.steps, scored = a.scored, C = a.ncrit;
+  const float* r = a.rew + ep * steps * n + j;  // r[t * n]
+  const float* q = a.q + (ep * steps * n + j) * C;  // q[t * n * C + c]
+  float* g = a.g + ep * steps * n + j;
+  const double gam = (double)a.gamma;
+  double G = 0.0;
+  for (int t = steps - 1; t >= 0; --t) {
+    G = (double)r[(int64_t)t * n] + gam * G;
+    g[(int64_t)t * n] = (float)G;
+  }
+  double s0 = 0.0, s1 = 0.0;
+  for (int b0 = 0; b0 < scored; b0 += EVR_B) {
+    G = 0.0;
+    for (int t = steps - 1; t >= b0 + EVR_B; --t) G = (double)r[(int64_t)t * n] + gam * G;
+    double gb[EVR_B];
+#pragma unroll
+    for (int k = EVR_B - 1; k >= 0; --k) {
+      const int t = b0 + k;
+      if (t < steps) G = (double)r[(int64_t)t * n] + gam * G;
+      gb[k] = G;
+    }
+#pragma unroll
+    for (int k = 0; k < EVR_B; ++k) {
+      const int t = b0 + k;
+      if (t < scored) {
+        s0 += (double)q[(int64_t)t * n * C] - gb[k];
+        if (C > 1) s1 += (double)q[(int64_t)t * n * C + 1] - gb[k];
+      }
+    }
+  }
+  const double inv = 1.0 / (double)scored;
+  a.gap[e * C] = (float)(inv * s0);
+  if (C > 1) a.gap[e * C + 1] = (float)(inv * s1);
 }
 
 // start states of episode ids [first, first + count) (mdp_eval_initial_state)
@@ -1412,6 +1507,8 @@ static void raise_lds_limits() {
   (void)hipFuncSetAttribute((const void*)k_eval_episodes<H>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
   (void)hipFuncSetAttribute((const void*)k_eval_episodes<H, EvalMuArgs>, hipFuncAttributeMaxDynamicSharedMemorySize,
                             128 * 1024);
+  (void)hipFuncSetAttribute((const void*)k_eval_episodes<H, EvalQArgs>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                            128 * 1024);
 }
 static void ensure_lds_limits() {
   if (!set_lds_limit_done) {
@@ -1473,6 +1570,27 @@ hipError_t mdp_launch_eval_matchups(const EvalMuArgs& a, int H, int lds_bytes, h
     case 256: return launch_eval_matchups_t<256>(a, lds_bytes, s);
     default: return hipErrorInvalidValue;
   }
+}
+template <int H>
+static hipError_t launch_eval_q_t(const EvalQArgs& a, int lds_bytes, hipStream_t s) {
+  mdp_launch(k_eval_episodes<H, EvalQArgs>, dim3((a.episodes + MDP_R - 1) / MDP_R), dim3(MDP_NT), lds_bytes, s, a);
+  MDP_CHECK_LAUNCH();
+  return hipSuccess;
+}
+hipError_t mdp_launch_eval_q(const EvalQArgs& a, int H, int lds_bytes, hipStream_t s) {
+  ensure_lds_limits();
+  switch (H) {
+    case 64: return launch_eval_q_t<64>(a, lds_bytes, s);
+    case 128: return launch_eval_q_t<128>(a, lds_bytes, s);
+    case 256: return launch_eval_q_t<256>(a, lds_bytes, s);
+    default: return hipErrorInvalidValue;
+  }
+}
+hipError_t mdp_launch_eval_returns(const EvalRetArgs& a, hipStream_t s) {
+  const int64_t total = (int64_t)a.episodes * a.n;
+  mdp_launch(k_eval_returns, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, a);
+  MDP_CHECK_LAUNCH();
+  return hipSuccess;
 }
 hipError_t mdp_launch_eval_reset(const EnvDesc& env, uint64_t seed, uint32_t first, int count, float* pos, float* vel,
                                  int32_t* goal, hipStream_t s) {

@@ -953,6 +953,62 @@ class Engine:
                    "min": r64.min(0).values.tolist(), "max": r64.max(0).values.tolist()}
         return {"returns": ret, "bench": rec, "summary": summary}
 
+    def eval_q_window(self, scored=None, tail=0.01):
+        """the default (steps, scored) of evaluate_q: scored = max_episode_len,
+        steps = scored + the smallest W with gamma^W <= tail (90 at gamma 0.95),
+        inside the call's step limit"""
+        scored = self.max_episode_len if scored is None else int(scored)
+        gamma, w = float(self.cfg.gamma), 1
+        while gamma ** w > tail and scored + w < _lib.EVAL_Q_MAX_STEPS:
+            w += 1
+        return scored + w, scored
+
+    def evaluate_q(self, episodes, steps=None, scored=None, first_episode=0, mode="sample", u=None):
+        """Score the live critics against the returns their policies then collect
+        (mdp_evaluate_q): evaluate's episode ids, played `steps` steps without
+        reset -- the reference never stores done = 1 for these scenarios, so a
+        critic estimates the continuing world's return -- with Q_j(o_t, a_t) of
+        every agent's critic (and its twin on a td3 engine: C = 2) taken in the
+        same launch.  The first `scored` steps are compared: their returns-to-go
+        lack at most a factor gamma^(steps - scored + 1) of the return's scale.
+        scored defaults to max_episode_len, steps to eval_q_window()'s.  u:
+        [episodes, steps, n, 5] injected uniforms (sample mode).  Nothing training
+        uses is read or written.  Returns a dict of float32 device tensors `q`
+        [episodes, steps, n, C], `rew` and `g` [episodes, steps, n] (step rewards;
+        return-to-go, formed in fp64), `gap` [episodes, n, C] (mean over the
+        scored steps of q - g), `steps`, `scored`, and `summary`: per agent and
+        critic ([n][C] lists, fp64) `q_mean` and `g_mean` over episodes and scored
+        steps, `gap_mean`, `gap_rms` (over episodes), and `truncation`."""
+        if mode not in _lib.EVAL_MODE:
+            raise ValueError(f"unknown evaluation mode {mode!r} (sample, mean)")
+        episodes, first_episode = int(episodes), int(first_episode)
+        if scored is None:
+            scored = self.max_episode_len if steps is None else min(self.max_episode_len, int(steps))
+        if steps is None:
+            steps = self.eval_q_window(scored)[0]
+        steps, scored = int(steps), int(scored)
+        C = 2 if self.td3 else 1
+        ne, ns = max(episodes, 0), max(steps, 0)
+        uu = None if u is None else u.to(self.device, torch.float32).contiguous()
+        self._sized("u", uu, ne * ns * self.n * _lib.ACT_DIM)
+        q = torch.empty((ne, ns, self.n, C), dtype=torch.float32, device=self.device)
+        rew = torch.empty((ne, ns, self.n), dtype=torch.float32, device=self.device)
+        g = torch.empty((ne, ns, self.n), dtype=torch.float32, device=self.device)
+        gap = torch.empty((ne, self.n, C), dtype=torch.float32, device=self.device)
+        self.sync_in()
+        self._c("mdp_evaluate_q", first_episode, episodes, _lib.EVAL_MODE[mode], steps, scored, self._ptr(uu),
+                self._ptr(q), self._ptr(rew), self._ptr(g), self._ptr(gap))
+        self._keep = (uu,)
+        self.sync_out()
+        gap64 = gap.double()
+        g_mean = g[:, :scored].double().mean((0, 1))
+        summary = {"q_mean": q[:, :scored].double().mean((0, 1)).tolist(),
+                   "g_mean": [[v] * C for v in g_mean.tolist()],
+                   "gap_mean": gap64.mean(0).tolist(),
+                   "gap_rms": gap64.pow(2).mean(0).sqrt().tolist(),
+                   "truncation": float(self.cfg.gamma) ** (steps - scored + 1)}
+        return {"q": q, "rew": rew, "g": g, "gap": gap, "steps": steps, "scored": scored, "summary": summary}
+
     def eval_initial_state(self, episodes, first_episode=0):
         """start states of those evaluation ids (mdp_eval_initial_state): pos / vel
         [episodes, n_entities, 2] float32, goal [episodes] int32 (host arrays)"""

@@ -174,6 +174,11 @@ class VecRunner:
         training's env copies, replay, log and counters are left alone"""
         return self.eng.evaluate(episodes, first_episode=first_episode, mode=mode, bench=bench)
 
+    def evaluate_q(self, episodes, steps=None, scored=None, first_episode=0, mode="sample"):
+        """score the live critics against the returns the policies then collect
+        on those ids (Engine.evaluate_q); leaves training alone as evaluate does"""
+        return self.eng.evaluate_q(episodes, steps=steps, scored=scored, first_episode=first_episode, mode=mode)
+
     def stats(self, agent):
         return self.eng.stats(agent)
 

@@ -102,6 +102,14 @@ def parse_args(argv=None):
                              "mode, one GPU, npz checkpoints; not with --prioritized-replay)")
     parser.add_argument("--policy-delay", type=int, default=2,
                         help="--td3: critic steps per policy / target update, 1..8 (1: twin critics without delay)")
+    parser.add_argument("--minimax", action="store_true", default=False,
+                        help="M3DDPG: in the critic target and the actor loss the other agents' actions move one "
+                             "normalised gradient step against this agent's Q (strict mode, one GPU; not with "
+                             "--td3 or --prioritized-replay)")
+    parser.add_argument("--adv-eps", type=float, default=1e-3,
+                        help="--minimax: perturbation rate for agents on the other side of --num-adversaries")
+    parser.add_argument("--adv-eps-s", type=float, default=1e-5,
+                        help="--minimax: perturbation rate for agents on the same side")
     # device-side policy evaluation (whole episodes in one launch; training state untouched)
     parser.add_argument("--evaluate", action="store_true", default=False,
                         help="load as --benchmark does and score the policies on evaluation episodes 0 .. "
@@ -387,10 +395,11 @@ def train(arglist):
     from maddpg_amd.common.tf_util import per_kwargs
     per = per_kwargs(arglist)
     td3_flags(arglist, world)
+    minimax_flags(arglist, world)
     try:
         runner = _make_runner(arglist, VecRunner, world, rank, per)
     except MdpError as e:      # e.g. prioritized replay with throughput mode or several GPUs
-        if not per and not arglist.td3:
+        if not per and not arglist.td3 and not arglist.minimax:
             raise
         raise SystemExit(str(e))
     return _train(arglist, runner, exp_name, world, rank)
@@ -413,8 +422,27 @@ def td3_flags(arglist, world=1):
         raise SystemExit("--td3 saves npz checkpoints only (the second critic has no reference variable names)")
 
 
+def minimax_flags(arglist, world=1):
+    """--minimax is M3DDPG on one GPU in strict mode: refuse the combinations the
+    library has no variant for before anything is built"""
+    if not getattr(arglist, "minimax", False):
+        return
+    for name in ("adv_eps", "adv_eps_s"):
+        v = getattr(arglist, name)
+        if not (v >= 0 and v != float("inf")):
+            raise SystemExit(f"--{name.replace('_', '-')} must be finite and >= 0")
+    if arglist.td3:
+        raise SystemExit("--minimax does not combine with --td3")
+    if arglist.prioritized_replay:
+        raise SystemExit("--minimax does not combine with --prioritized-replay")
+    if arglist.update_mode != "strict":
+        raise SystemExit("--minimax needs --update-mode strict")
+    if (arglist.num_gpus or 1) > 1 or world > 1:
+        raise SystemExit("--minimax runs on one GPU (--num-gpus 1)")
+
+
 def _make_runner(arglist, VecRunner, world, rank, per):
-    from maddpg_amd.common.tf_util import td3_kwargs
+    from maddpg_amd.common.tf_util import minimax_kwargs, td3_kwargs
     runner = VecRunner(arglist.scenario, arglist.num_envs, n_agents=arglist.num_agents,
                        scenario_adversaries=arglist.scenario_adversaries,
                        num_adversaries=arglist.num_adversaries, good_policy=arglist.good_policy,
@@ -426,7 +454,7 @@ def _make_runner(arglist, VecRunner, world, rank, per):
                        capacity=arglist.buffer_size,
                        # the learning-curve windows of one terminal step span <= save_rate + E episodes
                        episode_log_rows=max(4096, 4 * arglist.num_envs, arglist.save_rate + 2 * arglist.num_envs),
-                       **per, **td3_kwargs(arglist))
+                       **per, **td3_kwargs(arglist), **minimax_kwargs(arglist))
     if arglist.update_mode != "strict":
         runner.eng.set_update_mode(arglist.update_mode)
     return runner
@@ -536,6 +564,7 @@ def main(argv=None):
     argv = sys.argv[1:] if argv is None else list(argv)
     arglist = parse_args(argv)
     td3_flags(arglist)
+    minimax_flags(arglist)
     if arglist.num_gpus is not None:
         from maddpg_amd.launch import rank_launch_plan, run_ranks
         plan = rank_launch_plan(arglist.num_gpus, os.environ, os.path.abspath(__file__), argv,

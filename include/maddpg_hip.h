@@ -592,6 +592,39 @@ int mdp_td3_enable(mdp_handle* h, void* buf_dev, int64_t bytes, int32_t policy_d
  * of agent's last update; synchronises */
 int mdp_td3_info(mdp_handle* h, int32_t agent, double out4[4]);
 
+/* ---- M3DDPG: minimax critic targets and actor loss (Li et al., AAAI 2019; ----
+ * DESIGN.md section 20).  eps_host [n_agents][n_agents], row-major, finite and
+ * >= 0: eps[i][j] is agent i's perturbation rate for agent j's action (the
+ * diagonal is ignored).  With g_j the gradient of agent i's (target) Q to
+ * agent j's action of a batch row and ghat_j = g_j / sqrt(max(sum g_j^2,
+ * 1e-12)) over agent j's logical action entries:
+ *   critic step: q' = Q_tgt_i([o' | a~_i, (a~_j - eps[i][j] ghat_j)_{j != i}]), the
+ *                gradient taken at the unperturbed target actions; the TD line
+ *                and everything after it as without M3DDPG;
+ *   actor step:  p_loss = -mean Q_i([o | a_i, (a_j - eps[i][j] ghat_j)_{j != i}])
+ *                + the regulariser, the gradient taken at the replayed actions
+ *                and the sample a_i; the perturbation is a constant of the
+ *                backward.
+ * One linearised worst-case step, neither clipped nor renormalised; pad entries
+ * of a narrower agent's slot stay exact zeros.  An agent with a local (DDPG)
+ * critic sees no other action: its update is the one without M3DDPG, bit for
+ * bit; with every eps[i][*] = 0 agent i's update equals the MADDPG update of the
+ * general gradient kernels bit for bit.  mdp_get_stats: [1] the perturbed
+ * p_loss, [4] the mean of the perturbed q'.  Noise streams and counters are
+ * MADDPG's.  Enable comes before the handle's first update / train call.
+ * M3DDPG runs in strict mode on one GPU on the general gradient kernels;
+ * refused: prioritized replay, MATD3, throughput mode, mdp_update_all, data
+ * parallelism, and the phase entry points mdp_critic_grad / mdp_actor_grad /
+ * mdp_reduce_grad / mdp_apply_grad.  No new parameters: checkpoints and the
+ * evaluation entry points are unchanged. */
+int mdp_minimax_enable(mdp_handle* h, const float* eps_host);
+/* eps_out_host [n_agents][n_agents] as enabled (diagonal 0) */
+int mdp_minimax_info(mdp_handle* h, float* eps_out_host);
+/* debug: device buffers [batch_size][n_agents][MDP_ACT_DIM] (or NULL: none) that
+ * receive every agent's action as the second forward of the next critic /
+ * actor steps of a minimax agent reads it (the agent's own slot unperturbed) */
+int mdp_minimax_debug_adv(mdp_handle* h, float* critic_adv_dev, float* actor_adv_dev);
+
 /* ---- profiling: HIP events bracketing every launch of one kernel kind -- */
 enum mdp_kernel_kind {
     MDP_K_INDEX = 0, MDP_K_GATHER = 1, MDP_K_CRITIC_GRAD = 2, MDP_K_ACTOR_GRAD = 3,

@@ -177,6 +177,9 @@ SIGNATURES = {
     "mdp_td3_bytes": (_I64, [ctypes.POINTER(MdpConfig)]),
     "mdp_td3_enable": (ctypes.c_int, [_P, _P, _I64, _I32]),
     "mdp_td3_info": (ctypes.c_int, [_P, _I32, _F64P]),
+    "mdp_minimax_enable": (ctypes.c_int, [_P, _F32P]),
+    "mdp_minimax_info": (ctypes.c_int, [_P, _F32P]),
+    "mdp_minimax_debug_adv": (ctypes.c_int, [_P, _P, _P]),
     "mdp_prof_enable": (ctypes.c_int, [_P, _I32, _I32]),
     "mdp_prof_read": (ctypes.c_int, [_P, _I32, _F64P, ctypes.POINTER(_I64)]),
 }

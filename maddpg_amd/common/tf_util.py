@@ -70,7 +70,9 @@ class Session:
         seed = self.seed if self.seed is not None else int(getattr(args, "seed", 0) or 0)
         self._engine = Engine(obs_dims, local_q, num_units=args.num_units, batch_size=args.batch_size,
                               max_episode_len=args.max_episode_len, capacity=int(1e6), lr=args.lr,
-                              gamma=args.gamma, seed=seed, act_dims=t0.act_dims, **per_kwargs(args), **td3_kwargs(args))
+                              gamma=args.gamma, seed=seed, act_dims=t0.act_dims,
+                              num_adversaries=int(getattr(args, "num_adversaries", 0) or 0), **per_kwargs(args),
+                              **td3_kwargs(args), **minimax_kwargs(args))
         self._engine.init_params(seed)
         return self._engine
 
@@ -154,6 +156,13 @@ def td3_kwargs(args):
     if not getattr(args, "td3", False):
         return {}
     return dict(td3=True, policy_delay=getattr(args, "policy_delay", 2))
+
+
+def minimax_kwargs(args):
+    """Engine keywords of --minimax / --adv-eps / --adv-eps-s (experiments/train.py); {} when off"""
+    if not getattr(args, "minimax", False):
+        return {}
+    return dict(minimax=True, adv_eps=getattr(args, "adv_eps", 1e-3), adv_eps_s=getattr(args, "adv_eps_s", 1e-5))
 
 
 def per_kwargs(args):

@@ -423,6 +423,11 @@ struct mdp_handle {
   int64_t td3_work[MDP_MAX_AGENTS] = {};
   // graphs keyed by {kind (0 round, 1 step, 2 group), every agent's count mod d, the round counts}
   std::map<std::vector<int>, hipGraphExec_t> td3_exec;
+  // M3DDPG (mdp_minimax_enable): eps[i][j], and the debug buffers that receive
+  // the moved actions of the critic / actor step (mdp_minimax_debug_adv)
+  bool minimax = false;
+  float mm_eps[MDP_MAX_AGENTS][MDP_MAX_AGENTS] = {};
+  float *mm_adv_c = nullptr, *mm_adv_a = nullptr;
 };
 
 namespace {
@@ -748,6 +753,12 @@ CriticArgsPer per_critic_args(mdp_handle* h, const CriticArgs& a) {
   return p;
 }
 
+// M3DDPG: agent's steps run the minimax instantiations -- a MADDPG critic that
+// sees another agent's action (a DDPG critic sees none: today's kernels, bit for bit)
+bool mm_agent(const mdp_handle* h, int agent) {
+  return h->minimax && !h->L.topo.ag[agent].local_q && h->cfg.n_agents > 1;
+}
+
 int do_critic_grad(mdp_handle* h, int agent, const int32_t* idx, const float* u_tgt, int32_t* pf_out = nullptr,
                    bool tp = false, bool apre = false, const float* u_act = nullptr, int post_prev = -1,
                    int pf_n = 0, bool shared = false) {
@@ -764,6 +775,17 @@ int do_critic_grad(mdp_handle* h, int agent, const int32_t* idx, const float* u_
       HIPCHK(h, mdp_launch_critic_grad_r_per(per_critic_args(h, a), lds_critic_r_bytes(h->L.topo, agent), h->stream));
     else
       HIPCHK(h, mdp_launch_critic_grad_r(a, lds_critic_r_bytes(h->L.topo, agent), h->stream));
+    return 0;
+  }
+  if (mm_agent(h, agent) && !tp) {
+    CriticArgsMm m;
+    static_cast<CriticArgs&>(m) = a;
+    while (m.group > 1 && lds_critic_mm_bytes(h->L.topo, m.group) > MDP_LDS_BUDGET) --m.group;
+    const int lds = lds_critic_mm_bytes(h->L.topo, m.group);
+    if (lds > MDP_LDS_BUDGET) return fail(h, "minimax critic step does not fit in LDS");
+    for (int j = 0; j < MDP_MAX_AGENTS; ++j) m.eps[j] = h->mm_eps[agent][j];
+    m.adv_out = h->mm_adv_c;
+    HIPCHK(h, mdp_launch_critic_grad_mm(m, h->L.topo.H, lds, h->stream));
     return 0;
   }
   if (lds_critic_bytes(h->L.topo, a.group) > MDP_LDS_BUDGET) return fail(h, "critic step does not fit in LDS");
@@ -819,6 +841,14 @@ int do_actor_grad(mdp_handle* h, int agent, const int32_t* idx, const float* u_a
       lds = std::max(lds, lds_critic_pre_bytes(h->L.topo));
     }
     HIPCHK(h, mdp_launch_actor_grad_r(a, lds, h->stream));
+    return 0;
+  }
+  if (mm_agent(h, agent) && !tp) {
+    ActorArgsMm m;
+    static_cast<ActorArgs&>(m) = a;
+    for (int j = 0; j < MDP_MAX_AGENTS; ++j) m.eps[j] = h->mm_eps[agent][j];
+    m.adv_out = h->mm_adv_a;
+    HIPCHK(h, mdp_launch_actor_grad_mm(m, h->L.topo.H, lds_actor_mm_bytes(h->L.topo), h->stream));
     return 0;
   }
   HIPCHK(h, mdp_launch_actor_grad(a, h->L.topo.H, lds_actor_bytes(h->L.topo), h->stream));
@@ -1607,6 +1637,7 @@ int per_update(mdp_handle* h, int agent0, int agents, int count, const int32_t* 
 
 const char* kPerNoDp = "prioritized replay runs on one GPU in strict mode: no data-parallel exchange";
 const char* kTd3NoDp = "MATD3 (mdp_td3_enable) runs on one GPU in strict mode: no data-parallel exchange";
+const char* kMmNoDp = "M3DDPG (mdp_minimax_enable) runs on one GPU in strict mode: no data-parallel exchange";
 
 // byte offsets inside the caller's TD3 buffer
 struct Td3Layout {
@@ -2388,6 +2419,7 @@ int mdp_dp_init(mdp_handle* h, const uint8_t* id128, int32_t world, int32_t rank
   if (unusable(h) || !id128) return -1;
   if (h->per) return fail(h, kPerNoDp);
   if (h->td3) return fail(h, (std::string("mdp_dp_init: ") + kTd3NoDp).c_str());
+  if (h->minimax) return fail(h, (std::string("mdp_dp_init: ") + kMmNoDp).c_str());
   if (h->update_mode != 0) return fail(h, "join data parallelism before choosing the throughput mode");
   if (h->p2p || h->xbuf) return fail(h, "mdp_dp_init: the xGMI exchange is already set up");
   if (!rccl().ok) return fail(h, "librccl.so.1 could not be loaded");
@@ -2427,6 +2459,7 @@ int mdp_dp_xgmi_open(mdp_handle* h, int32_t world, int32_t rank, uint8_t* handle
   if (unusable(h) || !handle_out) return -1;
   if (h->per) return fail(h, kPerNoDp);
   if (h->td3) return fail(h, (std::string("mdp_dp_xgmi_open: ") + kTd3NoDp).c_str());
+  if (h->minimax) return fail(h, (std::string("mdp_dp_xgmi_open: ") + kMmNoDp).c_str());
   if (h->update_mode != 0) return fail(h, "join data parallelism before choosing the throughput mode");
   if (h->comm) return fail(h, "mdp_dp_xgmi_open: an RCCL communicator is already set up");
   if (h->xbuf) return fail(h, "mdp_dp_xgmi_open: already open");
@@ -2502,6 +2535,7 @@ int mdp_dp_xgmi_enable(mdp_handle* h) {
   if (!h->xd_dev) return fail(h, "mdp_dp_xgmi_enable: not connected");
   if (h->per) return fail(h, kPerNoDp);
   if (h->td3) return fail(h, (std::string("mdp_dp_xgmi_enable: ") + kTd3NoDp).c_str());
+  if (h->minimax) return fail(h, (std::string("mdp_dp_xgmi_enable: ") + kMmNoDp).c_str());
   if (h->update_mode != 0) return fail(h, "join data parallelism before choosing the throughput mode");
   HIPCHK(h, hipStreamSynchronize(h->stream));
   h->p2p = true;
@@ -2592,6 +2626,8 @@ int mdp_set_update_mode(mdp_handle* h, int32_t mode) {
   if (mode != 0 && mode != 1) return fail(h, "update mode must be 0 (strict) or 1 (throughput)");
   if (mode == 1) {
     if (h->td3) return fail(h, "mdp_set_update_mode: mode 1 (throughput) is not supported with MATD3 (mdp_td3_enable)");
+    if (h->minimax)
+      return fail(h, "mdp_set_update_mode: mode 1 (throughput) is not supported with M3DDPG (mdp_minimax_enable)");
     if (h->per) return fail(h, "prioritized replay needs the strict update mode (throughput mode is not supported)");
     if (!tp_ok(h)) return fail(h, "throughput mode needs the fused optimizer step for every net and <= 8 agents");
     HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -2608,6 +2644,7 @@ int mdp_set_update_mode(mdp_handle* h, int32_t mode) {
 int mdp_update_all(mdp_handle* h, const int32_t* idx_dev, const float* u_tgt_dev, const float* u_act_dev) {
   if (unusable(h)) return -1;
   if (h->td3) return fail(h, "mdp_update_all: throughput mode is not supported with MATD3 (mdp_td3_enable)");
+  if (h->minimax) return fail(h, "mdp_update_all: throughput mode is not supported with M3DDPG (mdp_minimax_enable)");
   if (h->update_mode != 1) return fail(h, "mdp_update_all: set throughput mode first");
   h->trained = true;
   if (h->len <= 0) return fail(h, "update on an empty replay buffer");
@@ -2626,6 +2663,12 @@ int mdp_update_all(mdp_handle* h, const int32_t* idx_dev, const float* u_tgt_dev
   return do_round_tp(h, idx, u_tgt_dev, u_act_dev, nullptr);
 }
 
+static const char* kMmNoPhase(const char* fn) {
+  static thread_local std::string m;
+  m = std::string(fn) + ": the phase entry points serve data parallelism; M3DDPG (mdp_minimax_enable) uses mdp_update";
+  return m.c_str();
+}
+
 static const char* kTd3NoPhase(const char* fn) {
   static thread_local std::string m;
   m = std::string(fn) + ": the phase entry points serve data parallelism; MATD3 (mdp_td3_enable) uses mdp_update";
@@ -2637,6 +2680,7 @@ int mdp_critic_grad(mdp_handle* h, int32_t agent, const int32_t* idx_dev, const 
   if (!idx_dev) return fail(h, "critic_grad needs indices");
   if (h->per) return fail(h, "mdp_critic_grad: the phase entry points serve data parallelism; prioritized replay uses mdp_update");
   if (h->td3) return fail(h, kTd3NoPhase("mdp_critic_grad"));
+  if (h->minimax) return fail(h, kMmNoPhase("mdp_critic_grad"));
   h->trained = true;
   MDP_DEV(h, idx_dev, 4 * (int64_t)h->cfg.batch_size, "mdp_critic_grad", false);
   MDP_DEV(h, u_tgt_dev, 4 * (int64_t)h->cfg.n_agents * h->cfg.batch_size * MDP_ACT_DIM, "mdp_critic_grad", true);
@@ -2647,6 +2691,7 @@ int mdp_actor_grad(mdp_handle* h, int32_t agent, const int32_t* idx_dev, const f
   if (bad_agent(h, agent)) return -1;
   if (!idx_dev) return fail(h, "actor_grad needs indices");
   if (h->td3) return fail(h, kTd3NoPhase("mdp_actor_grad"));
+  if (h->minimax) return fail(h, kMmNoPhase("mdp_actor_grad"));
   h->started = true;
   MDP_DEV(h, idx_dev, 4 * (int64_t)h->cfg.batch_size, "mdp_actor_grad", false);
   MDP_DEV(h, u_act_dev, 4 * (int64_t)h->cfg.batch_size * MDP_ACT_DIM, "mdp_actor_grad", true);
@@ -2656,12 +2701,14 @@ int mdp_actor_grad(mdp_handle* h, int32_t agent, const int32_t* idx_dev, const f
 int mdp_reduce_grad(mdp_handle* h, int32_t agent, int32_t net) {
   if (bad_agent(h, agent)) return -1;
   if (h->td3) return fail(h, kTd3NoPhase("mdp_reduce_grad"));
+  if (h->minimax) return fail(h, kMmNoPhase("mdp_reduce_grad"));
   return do_reduce(h, agent, net ? 1 : 0);
 }
 
 int mdp_apply_grad(mdp_handle* h, int32_t agent, int32_t net, float scale) {
   if (bad_agent(h, agent)) return -1;
   if (h->td3) return fail(h, kTd3NoPhase("mdp_apply_grad"));
+  if (h->minimax) return fail(h, kMmNoPhase("mdp_apply_grad"));
   return do_apply(h, agent, net ? 1 : 0, false, scale);
 }
 
@@ -3063,7 +3110,7 @@ static int step_launches(mdp_handle* h, int rounds) {
     for (int r = 0; r < rounds && !rc; ++r) rc = per_round_launches(h, r == 0);
     return rc;
   }
-  if (h->td3) {  // MATD3: one n B draw per round, no draw rides on another launch
+  if (h->td3 || h->minimax) {  // MATD3, M3DDPG: one n B draw per round, no draw rides on another launch
     int rc = env_step_launch(h, nullptr, nullptr);
     for (int r = 0; r < rounds && !rc; ++r) {
       if ((rc = launch_make_index(h, nb, h->index))) break;
@@ -3385,6 +3432,7 @@ int mdp_per_enable(mdp_handle* h, void* buf_dev, int64_t bytes, float alpha, flo
   MDP_NEED(h);
   if (h->per) return fail(h, "mdp_per_enable: already enabled");
   if (h->td3) return fail(h, "mdp_per_enable: prioritized replay and MATD3 (mdp_td3_enable) do not combine");
+  if (h->minimax) return fail(h, "mdp_per_enable: prioritized replay and M3DDPG (mdp_minimax_enable) do not combine");
   if (h->trained)
     return fail(h, "mdp_per_enable: call it before the handle's first update or train call");
   if (h->update_mode != 0)
@@ -3444,6 +3492,7 @@ int mdp_td3_enable(mdp_handle* h, void* buf_dev, int64_t bytes, int32_t policy_d
   if (h->trained) return fail(h, "mdp_td3_enable: call it before the handle's first update, round or train call");
   if (policy_delay < 1 || policy_delay > 8) return fail(h, "mdp_td3_enable: policy_delay must be in 1..8");
   if (h->per) return fail(h, "mdp_td3_enable: MATD3 and prioritized replay (mdp_per_enable) do not combine");
+  if (h->minimax) return fail(h, "mdp_td3_enable: MATD3 and M3DDPG (mdp_minimax_enable) do not combine");
   if (h->update_mode != 0)
     return fail(h, "mdp_td3_enable: MATD3 needs the strict update mode (throughput mode is not supported)");
   if (h->comm || h->p2p || h->xbuf || h->cfg.world_size > 1)
@@ -3496,6 +3545,64 @@ int mdp_td3_info(mdp_handle* h, int32_t agent, double out4[4]) {
   out4[1] = (double)(h->td3_count[agent] / h->td3_delay);
   out4[2] = q1;
   out4[3] = q2;
+  return 0;
+}
+
+// ----------------------------------------------------------------- M3DDPG
+int mdp_minimax_enable(mdp_handle* h, const float* eps_host) {
+  MDP_NEED(h);
+  if (h->minimax) return fail(h, "mdp_minimax_enable: already enabled");
+  if (h->trained)
+    return fail(h, "mdp_minimax_enable: call it before the handle's first update, round or train call");
+  if (!eps_host) return fail(h, "mdp_minimax_enable: eps_host is null");
+  const int n = h->cfg.n_agents;
+  for (int k = 0; k < n * n; ++k)
+    if (!std::isfinite(eps_host[k]) || eps_host[k] < 0.f)
+      return fail(h, "mdp_minimax_enable: eps_host must hold finite values >= 0");
+  if (h->per) return fail(h, "mdp_minimax_enable: M3DDPG and prioritized replay (mdp_per_enable) do not combine");
+  if (h->td3) return fail(h, "mdp_minimax_enable: M3DDPG and MATD3 (mdp_td3_enable) do not combine");
+  if (h->update_mode != 0)
+    return fail(h, "mdp_minimax_enable: M3DDPG needs the strict update mode (throughput mode is not supported)");
+  if (h->comm || h->p2p || h->xbuf || h->cfg.world_size > 1)
+    return fail(h, (std::string("mdp_minimax_enable: ") + kMmNoDp).c_str());
+  const Topo& T = h->L.topo;
+  if (T.H != 64 && T.H != 128 && T.H != 256)
+    return fail(h, "mdp_minimax_enable: the gradient kernels serve num_units 64, 128 or 256");
+  for (int i = 0; i < n; ++i) {
+    if (T.ag[i].local_q || n < 2) continue;
+    if (lds_critic_mm_bytes(T, 1) > MDP_LDS_BUDGET || lds_actor_mm_bytes(T) > MDP_LDS_BUDGET)
+      return fail(h, "mdp_minimax_enable: the minimax steps (the rows' gradient to every action column on top of "
+                     "the MADDPG steps' carve) do not fit the kernels' LDS envelope");
+  }
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  for (int i = 0; i < MDP_MAX_AGENTS; ++i)
+    for (int j = 0; j < MDP_MAX_AGENTS; ++j) h->mm_eps[i][j] = (i < n && j < n && i != j) ? eps_host[i * n + j] : 0.f;
+  h->minimax = true;
+  h->general_grads = true;  // M3DDPG runs on the general kernels: no actor_pre / critic_pre, no index prefetch
+  drop_graphs(h);
+  return 0;
+}
+
+int mdp_minimax_info(mdp_handle* h, float* eps_out_host) {
+  MDP_NEED(h);
+  if (!h->minimax) return fail(h, "mdp_minimax_info: M3DDPG is not enabled (mdp_minimax_enable)");
+  if (!eps_out_host) return fail(h, "mdp_minimax_info: eps_out_host is null");
+  const int n = h->cfg.n_agents;
+  for (int i = 0; i < n; ++i)
+    for (int j = 0; j < n; ++j) eps_out_host[i * n + j] = h->mm_eps[i][j];
+  return 0;
+}
+
+int mdp_minimax_debug_adv(mdp_handle* h, float* critic_adv_dev, float* actor_adv_dev) {
+  MDP_NEED(h);
+  if (!h->minimax) return fail(h, "mdp_minimax_debug_adv: M3DDPG is not enabled (mdp_minimax_enable)");
+  const int64_t bytes = 4 * (int64_t)h->cfg.batch_size * h->cfg.n_agents * MDP_ACT_DIM;
+  if (need_dev(h, critic_adv_dev, bytes, "mdp_minimax_debug_adv", "critic_adv_dev", true)) return -1;
+  if (need_dev(h, actor_adv_dev, bytes, "mdp_minimax_debug_adv", "actor_adv_dev", true)) return -1;
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  h->mm_adv_c = critic_adv_dev;
+  h->mm_adv_a = actor_adv_dev;
+  drop_graphs(h);  // the pointers are kernel arguments of the captured launches
   return 0;
 }
 

@@ -23,6 +23,12 @@
 // k_critic_grad<.., TWIN> (MATD3): the same up to the target critic, then
 //   || target critic 2 L1 || L2 || wave 0: heads, y from min(q1', q2'), Q1's loss seed
 //   || Q1 backward || Q2 forward L1 || L2 || head, loss seed on the same y || Q2 backward
+// k_critic_grad<.., MM> (M3DDPG): the same up to the target critic's layer 2, then
+//   || d2' = W3' masked || d1' = d2' W2'^T masked || dxa = d1' W1'[action rows]^T
+//   || a^_j = a~_j - eps_j ghat_j into xt || target critic L1 (action k-steps) || L2
+//   || wave 0: head, fp64 TD ... as the uniform kernel
+// k_actor_grad<.., MM>: after the critic's L2 the same three steps on the critic, a^ into
+//   the critic input, the critic's L1 and L2 again, then the uniform kernel's backward
 // k_actor_grad (maddpg.py:37-58):
 //   gather | actor L1 || L2 || head, Gumbel a_i, critic input || critic L1 || L2
 //   || head q, d2 || dh1c tiles || da, softmax backward + reg (wave 0)
@@ -329,6 +335,59 @@ __device__ __forceinline__ void dgrad_tile_relu(const float* dY, int ldy, int N,
   }
 }
 
+// Minimax: out[16][tile nt of ncols] = dY[16][N] @ W[kk0 + c][:]^T, the
+// gradient to the input columns kk0 .. kk0 + ncols of a layer W[K][N] (N a
+// multiple of 64), unmasked; contiguous transposed fragments (load_wchunk_tc)
+__device__ __forceinline__ void dgrad_tile_rows(const float* dY, int ldy, int N, const float* __restrict__ W, int kk0,
+                                                int ncols, float* out, int ldo, int nt) {
+  const int lane = threadIdx.x & 63, r = lane & 15, kq = lane >> 4;
+  const int col = nt * 16 + r;
+  const int kk = kk0 + min(col, ncols - 1);
+  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+  f32x4 wa[4], wb[4];
+  load_wchunk_tc(wa, W, N, kk, 0, kq);
+  for (int c0 = 0; c0 < N; c0 += 64) {
+    const bool more = c0 + 64 < N;
+    if (more) load_wchunk_tc(wb, W, N, kk, c0 + 64, kq);
+    acc = mfma_chunk_tc(acc, wa, dY, ldy, r, c0, kq);
+    if (more) {
+#pragma unroll
+      for (int m = 0; m < 4; ++m) wa[m] = wb[m];
+    }
+  }
+  if (col < ncols) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) out[(kq * 4 + i) * ldo + col] = acc[i];
+  }
+}
+
+// Minimax: the other agents' actions of the 16 rows, X[row][a0 + 5 j ..], moved
+// by -eps[j] ghat_j, ghat_j = g_j / sqrt(max(sum g_j^2, 1e-12)) over agent j's
+// logical entries in index order (TF's l2_normalize); agent `self` and the pad
+// entries stay as they are.  adv (or null): every agent's resulting slot,
+// [B][n][MDP_ACT_DIM]
+__device__ __forceinline__ void mm_perturb(const Topo& T, int self, const float* eps, const float* dxa, int lda,
+                                           float* X, int ldx, int a0, float* __restrict__ adv, int r0, int nvalid) {
+#pragma clang fp contract(off)
+  for (int e = threadIdx.x; e < MDP_R * T.n; e += blockDim.x) {
+    const int j = e / MDP_R, row = e - j * MDP_R;
+    float* xa = X + row * ldx + a0 + MDP_ACT_DIM * j;
+    if (j != self) {
+      const float* g = dxa + row * lda + MDP_ACT_DIM * j;
+      const int kj = topo_act_w(T, j);
+      float ss = 0.f;
+      for (int k = 0; k < kj; ++k) ss = ss + g[k] * g[k];
+      const float inv = 1.0f / sqrtf(fmaxf(ss, 1e-12f));
+      const float ej = eps[j];
+      for (int k = 0; k < kj; ++k) xa[k] = xa[k] - ej * (g[k] * inv);
+    }
+    if (adv && row < nvalid) {
+      float* o = adv + ((int64_t)(r0 + row) * T.n + j) * MDP_ACT_DIM;
+      for (int k = 0; k < MDP_ACT_DIM; ++k) o[k] = xa[k];
+    }
+  }
+}
+
 // dW[K][N] tile t = (mt, nt) of X^T[K][16] @ dY[16][N], to global (stride N); rows >= K not written
 __device__ __forceinline__ void wgrad_tile(const float* X, int ldx, int K, const float* dY, int ldy, int N,
                                            float* __restrict__ dW, int t) {
@@ -393,8 +452,12 @@ __device__ __forceinline__ void critic_backward(const float* th, const NDesc& nd
 // TWIN (A = CriticArgsTwin): the MATD3 step -- both target critics on the same
 // [o' | a~], y from the smaller, then critic 1's and critic 2's loss seed and
 // backward one after the other on the same activation slots
-template <int H, bool PER = false, class A = CriticArgs, bool TWIN = false>
+// MM (A = CriticArgsMm): the M3DDPG step -- after the target critic's forward its
+// backward to the other agents' target actions, those moved against Q', and the
+// target critic again on the moved input; strict mode, MADDPG critics
+template <int H, bool PER = false, class A = CriticArgs, bool TWIN = false, bool MM = false>
 __device__ __forceinline__ void critic_body(const A& a, const Topo& T, const int blk) {
+  static_assert(!(MM && (TWIN || PER)), "minimax combines with neither twin critics nor prioritized replay");
   // (no MDP_KARG_TOUCH here: at H = 128 it turned the kernel's 47 spilled
   // SGPRs into 91 spilled VGPRs)
   constexpr int NT = H / 16;
@@ -415,6 +478,8 @@ __device__ __forceinline__ void critic_body(const A& a, const Topo& T, const int
                                                                     // work-queue counter (fwd_phase_l12)
   float* ys = nullptr;  // TWIN: the rows' fp32 TD target, kept for critic 2's loss seed
   if constexpr (TWIN) ys = cv.take(MDP_R);
+  float* dxa = nullptr;  // MM: d q' / d (action columns) of the rows
+  if constexpr (MM) dxa = cv.take(MDP_R * MDP_ACT_DIM * T.n);
 
   const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63, nw = blockDim.x >> 6;
   const int r0 = blk * MDP_R;
@@ -614,11 +679,43 @@ __device__ __forceinline__ void critic_body(const A& a, const Topo& T, const int
     }
     __syncthreads();
     if (wave < NT) {
-      if (H / 4 <= 32 && wave == 0) head_load<HKS>(thw, thb, P + nd.t[4].off, P + nd.t[5].off, 1);
+      if (!MM && H / 4 <= 32 && wave == 0) head_load<HKS>(thw, thb, P + nd.t[4].off, P + nd.t[5].off, 1);
       fwd_tile_pf<true>(hA, ldh, 0, H, P + nd.t[2].off, P + nd.t[3].off, H, nullptr, 0, hB, ldh, wave, pf);
-      if constexpr (!TWIN) pf_load_t(pft, a.theta + nd.t[2].off, H, wave);  // the backward's dh1 = d2 W2^T
+      if constexpr (MM) pf_load_t(pft, P + nd.t[2].off, H, wave);  // the target critic's own d1 = d2 W2'^T
+      else if constexpr (!TWIN) pf_load_t(pft, a.theta + nd.t[2].off, H, wave);  // the backward's dh1 = d2 W2^T
     }
     __syncthreads();
+    if constexpr (MM) {
+      // rows are independent (seed 1 each): d2 = W3' masked by h2' in place (hB
+      // slot 0), d1 = (d2 W2'^T) masked by h1' in place (hA slot 0: an output
+      // needs only its own mask entry), dxa = d1 W1'[action rows]^T
+      const float w3t = P[nd.t[4].off + tid % H];
+      for (int r = tid / H, h = tid % H; r < MDP_R; r += MDP_GEN_THREADS / H)
+        hB[r * ldh + h] = hB[r * ldh + h] > 0.f ? w3t : 0.f;
+      __syncthreads();
+      if (wave < NT) dgrad_tile_relu_pf(hB, ldh, H, P + nd.t[2].off, hA, ldh, hA, ldh, wave, pft);
+      __syncthreads();
+      const int nac = MDP_ACT_DIM * T.n;
+      if (wave < (nac + 15) / 16) dgrad_tile_rows(hA, ldh, H, P + nd.t[0].off, T.sum_obs, nac, dxa, nac, wave);
+      __syncthreads();
+      mm_perturb(T, a.agent, a.eps, dxa, nac, xt, ldc, T.sum_obs, a.adv_out, r0, nvalid);
+      __syncthreads();
+      // the target critic on [o' | a^]: the first forward's calls (layer 1 again
+      // from the obs' partial where there is one), so eps = 0 repeats it bit for bit
+      if (wave < NT) {
+        pf_load(pf, P + nd.t[0].off, H, wave, tpre ? T.sum_obs : 0, ag.cin);
+        fwd_tile_pf<true>(xt, ldc, tpre ? T.sum_obs : 0, ag.cin, P + nd.t[0].off, P + nd.t[1].off, H,
+                          tpre ? xl : nullptr, ldh, hA, ldh, wave, pf);
+        pf_load(pf, P + nd.t[2].off, H, wave, 0, H);
+      }
+      __syncthreads();
+      if (wave < NT) {
+        if (H / 4 <= 32 && wave == 0) head_load<HKS>(thw, thb, P + nd.t[4].off, P + nd.t[5].off, 1);
+        fwd_tile_pf<true>(hA, ldh, 0, H, P + nd.t[2].off, P + nd.t[3].off, H, nullptr, 0, hB, ldh, wave, pf);
+        pf_load_t(pft, a.theta + nd.t[2].off, H, wave);  // the backward's dh1 = d2 W2^T
+      }
+      __syncthreads();
+    }
     if constexpr (TWIN) {
       // q1' off hB slot 0 (wave 0, today's head) while the tile waves run target
       // critic 2's layer 1 on the same xt into hA slot 0 (free since the layer
@@ -745,13 +842,18 @@ __device__ __forceinline__ void critic_body(const A& a, const Topo& T, const int
 
 // PER: the prioritized-replay twin (A = CriticArgsPer), strict mode only
 // TWIN: the MATD3 twin (A = CriticArgsTwin), strict mode only
-template <int H, bool PER = false, class A = CriticArgs, bool TWIN = false>
+// MM: the M3DDPG twin (A = CriticArgsMm), strict mode only
+template <int H, bool PER = false, class A = CriticArgs, bool TWIN = false, bool MM = false>
 __global__ __launch_bounds__(MDP_GEN_THREADS) void k_critic_grad(A a) {
-  critic_body<H, PER, A, TWIN>(a, a.topo, blockIdx.x);
+  critic_body<H, PER, A, TWIN, MM>(a, a.topo, blockIdx.x);
 }
 
 // AA: ActorArgs, or the Topo-less ActorArgsHead of a gradient-pair launch
-template <int H, class AA>
+// MM (AA = ActorArgsMm): the M3DDPG step -- after the critic's forward its
+// backward to the other agents' replayed actions, those moved against Q (a
+// constant of the backward), the critic again on the moved input, and the
+// step's backward from there
+template <int H, class AA, bool MM = false>
 __device__ __forceinline__ void actor_body(const AA& a, const Topo& T, const int blk) {
   constexpr int NT = H / 16;
   extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -773,6 +875,8 @@ __device__ __forceinline__ void actor_body(const AA& a, const Topo& T, const int
   float* dl = cv.take(MDP_R * 8);
   float* qv = cv.take(MDP_R * 8);
   float* w1ai = cv.take(MDP_ACT_DIM * H);  // the critic's layer-1 rows of the a_i input (for da)
+  float* dxa = nullptr;  // MM: d q / d (action columns) of the rows
+  if constexpr (MM) dxa = cv.take(MDP_R * MDP_ACT_DIM * T.n);
 
   const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63, nw = blockDim.x >> 6;
   const int r0 = blk * MDP_R;
@@ -898,11 +1002,70 @@ __device__ __forceinline__ void actor_body(const AA& a, const Topo& T, const int
   if (wave < NT) {
     fwd_tile_pf<true>(h1c, ldh, 0, H, P + nc.t[2].off, P + nc.t[3].off, H, nullptr, 0, h2c, ldh, wave, pf);
     pf_load_t(pft, P + nc.t[2].off, H, wave);  // dh1c = d2 W2c^T
-  } else if (H / 4 <= 32 && wave == nw - 1) {
+  } else if (!MM && H / 4 <= 32 && wave == nw - 1) {
     head_load<HKS>(qw, qb, P + nc.t[4].off, P + nc.t[5].off, 1);
   }
   __syncthreads();
   MDP_STAMP(38);
+  if constexpr (MM) {
+    // rows are independent (seed 1 each, no 1/B): d2 = W3c masked by h2c, d1 =
+    // (d2 W2c^T) masked by h1c, dxa = d1 W1c[action rows]^T; then the critic
+    // again with the other agents' actions moved in its input (the row prefix,
+    // or x), by the first forward's own calls: eps = 0 repeats it bit for bit
+    for (int r = tid / H, h = tid % H; r < MDP_R; r += MDP_GEN_THREADS / H)
+      d2[r * ldh + h] = h2c[r * ldh + h] > 0.f ? w3h : 0.f;
+    __syncthreads();
+    if (wave < NT) dgrad_tile_relu_pf(d2, ldh, H, P + nc.t[2].off, h1c, ldh, d1, ldh, wave, pft);
+    __syncthreads();
+    const int nac = MDP_ACT_DIM * T.n;
+    if (wave < (nac + 15) / 16) dgrad_tile_rows(d1, ldh, H, P + nc.t[0].off, T.sum_obs, nac, dxa, nac, wave);
+    if (pw) pf_load(pf, P + nc.t[0].off, H, wave - NT, 0, cin);
+    else if (!par && wave < NT) pf_load(pf, P + nc.t[0].off, H, wave, 0, cin);
+    __syncthreads();
+    if (par) mm_perturb(T, a.agent, a.eps, dxa, nac, rowbuf, ldr, T.sum_obs, nullptr, r0, nvalid);
+    else mm_perturb(T, a.agent, a.eps, dxa, nac, x, ldc, T.sum_obs, a.adv_out, r0, nvalid);
+    __syncthreads();
+    if (par && a.adv_out) {  // (the row prefix holds the replayed a_i; the input's a_i is the sample)
+      for (int e = tid; e < nvalid * nac; e += blockDim.x) {
+        const int row = e / nac, c = e - row * nac;
+        a.adv_out[(int64_t)(r0 + row) * nac + c] =
+            c / MDP_ACT_DIM == a.agent ? av[row * 8 + c % MDP_ACT_DIM] : rowbuf[row * ldr + T.sum_obs + c];
+      }
+    }
+    if (par) {
+      if (pw) {
+        const float* W1c = P + nc.t[0].off;
+        const int r = lane & 15, kq = lane >> 4;
+        pacc = f32x4{0.f, 0.f, 0.f, 0.f};
+        for (int c0 = 0; c0 < cin; c0 += 4 * MDP_KC) {
+          pacc = mfma_chunk_zc(pacc, pf, rowbuf, ldr, r, c0, cin, kq, a_lo, a_lo + MDP_ACT_DIM);
+          if (c0 + 4 * MDP_KC < cin) load_wchunk(pf, W1c, H, pcol, c0 + 4 * MDP_KC, cin, kq);
+        }
+#pragma unroll
+        for (int q = 0; q < 2; ++q) {
+          const int k = a4 + 4 * q + kq;
+          const float xa = (k >= a_lo && k < a_lo + MDP_ACT_DIM) ? av[r * 8 + (k - a_lo)] : 0.f;
+          if (a4 + 4 * q < cin) pacc = MDP_MFMA(xa, paw[q], pacc);
+        }
+        const float bias = P[nc.t[1].off + pcol];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) h1c[(kq * 4 + i) * ldh + pcol] = fmaxf(pacc[i] + bias, 0.f);
+      } else if (wave < NT) {
+        pf_load(pf, P + nc.t[2].off, H, wave, 0, H);
+      }
+    } else if (wave < NT) {
+      fwd_tile_pf<true, true>(x, ldc, 0, cin, P + nc.t[0].off, P + nc.t[1].off, H, nullptr, 0, h1c, ldh, wave, pf);
+      pf_load(pf, P + nc.t[2].off, H, wave, 0, H);
+    }
+    __syncthreads();
+    if (wave < NT) {
+      fwd_tile_pf<true>(h1c, ldh, 0, H, P + nc.t[2].off, P + nc.t[3].off, H, nullptr, 0, h2c, ldh, wave, pf);
+      pf_load_t(pft, P + nc.t[2].off, H, wave);  // dh1c = d2 W2c^T
+    } else if (H / 4 <= 32 && wave == nw - 1) {
+      head_load<HKS>(qw, qb, P + nc.t[4].off, P + nc.t[5].off, 1);
+    }
+    __syncthreads();
+  }
   // dL/dq = -1/B ; d2 = dq * W3c masked by h2c > 0.  q (the loss value only)
   // waits for the next phase, on a wave the dh1c tiles leave idle
   const bool q_late = NT < nw;
@@ -1004,11 +1167,14 @@ __device__ __forceinline__ void actor_body(const AA& a, const Topo& T, const int
   MDP_STAMP(60);
 }
 
-template <int H>
-__global__ __launch_bounds__(MDP_GEN_THREADS) void k_actor_grad(ActorArgs a) {
-  MDP_KARG_TOUCH("s"(a.agent), "s"(a.slab_stride), "s"(a.cpre_agent), "s"(a.topo.n));
-  MDP_KARG_TOUCH(MDP_KARG_ADESC(a.topo.ag[a.agent]));
-  actor_body<H>(a, a.topo, blockIdx.x);
+// MM: the M3DDPG twin (AA = ActorArgsMm), strict mode only
+template <int H, class AA = ActorArgs, bool MM = false>
+__global__ __launch_bounds__(MDP_GEN_THREADS) void k_actor_grad(AA a) {
+  if constexpr (!MM) {
+    MDP_KARG_TOUCH("s"(a.agent), "s"(a.slab_stride), "s"(a.cpre_agent), "s"(a.topo.n));
+    MDP_KARG_TOUCH(MDP_KARG_ADESC(a.topo.ag[a.agent]));
+  }
+  actor_body<H, AA, MM>(a, a.topo, blockIdx.x);
 }
 
 // throughput mode: agent i's critic step (workgroups [0, B/16)) and actor step
@@ -1058,6 +1224,31 @@ hipError_t launch_critic_twin(const CriticArgsTwin& a, int lds, hipStream_t s) {
   }
   mdp_launch(k_critic_grad<H, false, CriticArgsTwin, true>, dim3((a.B + MDP_R - 1) / MDP_R), dim3(MDP_GEN_THREADS), lds,
              s, a);
+  return hipGetLastError();
+}
+template <int H>
+hipError_t launch_critic_mm(const CriticArgsMm& a, int lds, hipStream_t s) {
+  static bool attr = false;
+  if (!attr) {
+    (void)hipFuncSetAttribute((const void*)k_critic_grad<H, false, CriticArgsMm, false, true>,
+                              hipFuncAttributeMaxDynamicSharedMemorySize, MDP_LDS_BUDGET);
+    (void)hipGetLastError();
+    attr = true;
+  }
+  mdp_launch(k_critic_grad<H, false, CriticArgsMm, false, true>, dim3((a.B + MDP_R - 1) / MDP_R),
+             dim3(MDP_GEN_THREADS), lds, s, a);
+  return hipGetLastError();
+}
+template <int H>
+hipError_t launch_actor_mm(const ActorArgsMm& a, int lds, hipStream_t s) {
+  static bool attr = false;
+  if (!attr) {
+    (void)hipFuncSetAttribute((const void*)k_actor_grad<H, ActorArgsMm, true>,
+                              hipFuncAttributeMaxDynamicSharedMemorySize, MDP_LDS_BUDGET);
+    (void)hipGetLastError();
+    attr = true;
+  }
+  mdp_launch(k_actor_grad<H, ActorArgsMm, true>, dim3((a.B + MDP_R - 1) / MDP_R), dim3(MDP_GEN_THREADS), lds, s, a);
   return hipGetLastError();
 }
 template <int H>
@@ -1117,6 +1308,22 @@ hipError_t mdp_launch_critic_grad_twin(const CriticArgsTwin& a, int H, int lds_b
     case 64: return launch_critic_twin<64>(a, lds_bytes, s);
     case 128: return launch_critic_twin<128>(a, lds_bytes, s);
     case 256: return launch_critic_twin<256>(a, lds_bytes, s);
+    default: return hipErrorInvalidValue;
+  }
+}
+hipError_t mdp_launch_critic_grad_mm(const CriticArgsMm& a, int H, int lds_bytes, hipStream_t s) {
+  switch (H) {
+    case 64: return launch_critic_mm<64>(a, lds_bytes, s);
+    case 128: return launch_critic_mm<128>(a, lds_bytes, s);
+    case 256: return launch_critic_mm<256>(a, lds_bytes, s);
+    default: return hipErrorInvalidValue;
+  }
+}
+hipError_t mdp_launch_actor_grad_mm(const ActorArgsMm& a, int H, int lds_bytes, hipStream_t s) {
+  switch (H) {
+    case 64: return launch_actor_mm<64>(a, lds_bytes, s);
+    case 128: return launch_actor_mm<128>(a, lds_bytes, s);
+    case 256: return launch_actor_mm<256>(a, lds_bytes, s);
     default: return hipErrorInvalidValue;
   }
 }

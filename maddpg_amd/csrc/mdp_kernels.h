@@ -76,6 +76,19 @@ struct CriticArgsTwin : CriticArgs {
   double* slab_stat2;
 };
 
+// M3DDPG (strict mode, general kernels): the argument blocks of the
+// gradient kernels' minimax instantiations.  eps[j] is this agent's
+// perturbation rate for agent j's action (row `agent` of the handle's matrix;
+// eps[agent] is ignored).  The critic step moves the other agents' target
+// actions, the actor step their replayed actions, by -eps[j] ghat_j, ghat_j
+// the l2-normalised gradient of this agent's (target) Q to that action, then
+// evaluates the step at the moved point.  adv_out [B][n][MDP_ACT_DIM] (or null)
+// receives every agent's action as the second forward reads it
+struct CriticArgsMm : CriticArgs {
+  float eps[MDP_MAX_AGENTS];
+  float* adv_out;
+};
+
 // precomputed critic-step work of one batch row (k_actor_grad_r's extra
 // workgroups -> k_critic_grad_r in critic_post mode):
 //   h1 [64] | h2 [64] (critic forward) | target-critic L1 accumulator [64] | q | pad 3 | a~ [16]
@@ -117,6 +130,10 @@ struct ActorArgsHead {
 };
 struct ActorArgs : ActorArgsHead {
   Topo topo;
+};
+struct ActorArgsMm : ActorArgs {  // M3DDPG, as CriticArgsMm
+  float eps[MDP_MAX_AGENTS];
+  float* adv_out;
 };
 
 // throughput mode on the general kernels: agent i's critic step and actor step
@@ -415,6 +432,10 @@ inline int lds_actor_bytes(const Topo& t) {
   const int R = 16, ldr = mdp_ld(t.row_stride), ldc = mdp_ld(t.cin_max), S = R * (t.H + 1);
   return 4 * (mdp_r4(R * ldr) + mdp_r4(R * ldc) + 6 * mdp_r4(S) + 5 * mdp_r4(R * 8) + mdp_r4(5 * t.H));
 }
+// the minimax instantiations keep the rows' gradient to every action column
+inline int lds_mm_dxa(const Topo& t) { return mdp_r4(16 * MDP_ACT_DIM * t.n); }
+inline int lds_critic_mm_bytes(const Topo& t, int G) { return lds_critic_bytes(t, G) + 4 * lds_mm_dxa(t); }
+inline int lds_actor_mm_bytes(const Topo& t) { return lds_actor_bytes(t) + 4 * lds_mm_dxa(t); }
 #define MDP_LDS_BUDGET (160 * 1024)
 // fast (register-resident, H = 64) variants in mdp_grads_r.hip
 inline int lds_critic_r_bytes(const Topo& t, int agent) {
@@ -496,6 +517,8 @@ hipError_t mdp_launch_grad_pair(const GradPairArgs& a, int H, int lds_bytes, hip
 hipError_t mdp_launch_critic_grad_r(const CriticArgs& a, int lds_bytes, hipStream_t s);
 hipError_t mdp_launch_critic_grad_per(const CriticArgsPer& a, int H, int lds_bytes, hipStream_t s);
 hipError_t mdp_launch_critic_grad_twin(const CriticArgsTwin& a, int H, int lds_bytes, hipStream_t s);
+hipError_t mdp_launch_critic_grad_mm(const CriticArgsMm& a, int H, int lds_bytes, hipStream_t s);
+hipError_t mdp_launch_actor_grad_mm(const ActorArgsMm& a, int H, int lds_bytes, hipStream_t s);
 hipError_t mdp_launch_critic_grad_r_per(const CriticArgsPer& a, int lds_bytes, hipStream_t s);
 hipError_t mdp_launch_actor_grad_r(const ActorArgs& a, int lds_bytes, hipStream_t s);
 hipError_t mdp_launch_rollout(const RolloutArgs& a, int H, int lds_bytes, hipStream_t s);

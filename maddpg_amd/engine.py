@@ -62,8 +62,14 @@ class Engine:
                  gamma=0.95, tau=1e-2, grad_clip=0.5, actor_reg=1e-3, adam_b1=0.9, adam_b2=0.999,
                  adam_eps=1e-8, seed=0, world_size=1, rank=0, device=None, episode_log_rows=0,
                  prioritized=False, per_alpha=0.6, per_beta0=0.4, per_beta_inc=0.001, per_eps=0.01,
-                 per_abs_err_upper=1.0, act_dims=None, td3=False, policy_delay=2):
-        """td3: MATD3 (mdp_td3_enable) -- twin critics, the TD target from the smaller
+                 per_abs_err_upper=1.0, act_dims=None, td3=False, policy_delay=2, minimax=False, adv_eps=1e-3,
+                 adv_eps_s=1e-5, minimax_eps=None):
+        """minimax: M3DDPG (mdp_minimax_enable) -- in the critic target and the actor
+        loss the other agents' actions move one normalised gradient step against
+        this agent's Q; rates adv_eps across the sides of num_adversaries and
+        adv_eps_s within a side, or minimax_eps, an n x n array eps[i][j] (which
+        alone also enables it); strict mode, one GPU, no prioritized replay, no td3.
+        td3: MATD3 (mdp_td3_enable) -- twin critics, the TD target from the smaller
         target critic, the actor and the targets updated every policy_delay-th
         critic step (1..8); strict mode, one GPU, no prioritized replay.
         act_dims: per-agent action widths A_i in 1..5 (Discrete(A_i)); None: 5 for
@@ -163,10 +169,19 @@ class Engine:
         if self.prioritized and self.td3:
             self.close()
             raise _lib.MdpError("td3 and prioritized replay do not combine (mdp_td3_enable)")
+        self.minimax = bool(minimax) or minimax_eps is not None
+        self.minimax_eps = None
+        if self.minimax and (self.prioritized or self.td3):
+            self.close()
+            raise _lib.MdpError("minimax combines with neither prioritized replay nor td3 (mdp_minimax_enable)")
         if self.prioritized:
             self._per_enable(per_alpha, per_beta0, per_beta_inc, per_eps, per_abs_err_upper)
         if self.td3:
             self._td3_enable(self.policy_delay)
+        if self.minimax:
+            from .envs import minimax_eps as _eps
+            self._minimax_enable(_eps(n, int(num_adversaries), adv_eps, adv_eps_s) if minimax_eps is None
+                                 else minimax_eps)
 
     # ------------------------------------------------------------ plumbing
     def _c(self, name, *args):
@@ -521,6 +536,38 @@ class Engine:
             self.td3_buf = None
             self.close()
             raise
+
+    # -------------------------------------------------------------- M3DDPG
+    def _minimax_enable(self, eps):
+        """minimax critic targets and actor loss (mdp_minimax_enable) with the rates
+        eps [n][n]; before the first update / train call"""
+        eps = np.ascontiguousarray(np.asarray(eps, np.float32))
+        if eps.shape != (self.n, self.n):
+            self.close()
+            raise ValueError(f"minimax_eps has shape {eps.shape} for {self.n} agents")
+        try:
+            self._c("mdp_minimax_enable", _lib.fptr(eps))
+        except _lib.MdpError:
+            self.close()
+            raise
+        self.minimax_eps = self.minimax_info()
+
+    def minimax_info(self):
+        """eps [n][n] as enabled, diagonal 0 (mdp_minimax_info)"""
+        out = np.zeros((self.n, self.n), np.float32)
+        self._c("mdp_minimax_info", _lib.fptr(out))
+        return out
+
+    def minimax_debug_adv(self, critic=True, actor=True):
+        """debug buffers [B][n][5] (float32, device) that receive the actions the second
+        forward of the next minimax critic / actor steps reads (mdp_minimax_debug_adv);
+        returns (critic_adv, actor_adv), None where not asked for"""
+        with torch.cuda.device(self.device):
+            bufs = [torch.zeros(self.batch_size, self.n, _lib.ACT_DIM, dtype=torch.float32, device=self.device)
+                    if on else None for on in (critic, actor)]
+        self._c("mdp_minimax_debug_adv", *[None if b is None else self._ptr(b) for b in bufs])
+        self._adv_bufs = bufs   # keep them alive while the handle points at them
+        return tuple(bufs)
 
     TD3_REGIONS = ("theta2", "target2", "adam_m2", "adam_v2", "grad2")
 

@@ -9,6 +9,8 @@ The physics itself runs in ``k_rollout`` (maddpg_amd/csrc/mdp_kernels.hip).
 from dataclasses import dataclass, field
 from typing import List
 
+import numpy as np
+
 ACT_DIM = 5
 
 
@@ -67,6 +69,19 @@ def spec(name, n_agents=None, num_adversaries=None):
         # listener sees its velocity, the 3 landmarks and the word (restated: parity UNPINNED)
         return ScenarioSpec(name, 2, 0, [3, 11], [3, 5])
     raise ValueError(f"unknown scenario {name!r}")
+
+
+def minimax_eps(n_agents, num_adversaries, adv_eps=1e-3, adv_eps_s=1e-5):
+    """M3DDPG's perturbation rates eps[i][j] (--minimax): adv_eps where agents i and j
+    stand on opposite sides (the first num_adversaries agents are the adversaries),
+    adv_eps_s where they stand on the same side; the diagonal is 0 (ignored)."""
+    na = max(0, min(int(n_agents), int(num_adversaries)))
+    eps = np.zeros((n_agents, n_agents), np.float32)
+    for i in range(n_agents):
+        for j in range(n_agents):
+            if i != j:
+                eps[i, j] = adv_eps if (i < na) != (j < na) else adv_eps_s
+    return eps
 
 
 def bench_record(sp, row, i):

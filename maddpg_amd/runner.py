@@ -46,9 +46,12 @@ class VecRunner:
                  num_units=64, lr=1e-2, gamma=0.95, max_episode_len=25, capacity=int(1e6), seed=0,
                  train_every=100, world_size=1, rank=0, device=None, episode_log_rows=0, tau=1e-2,
                  grad_clip=0.5, actor_reg=1e-3, prioritized=False, per_alpha=0.6, per_beta0=0.4,
-                 per_beta_inc=0.001, per_eps=0.01, per_abs_err_upper=1.0, td3=False, policy_delay=2):
+                 per_beta_inc=0.001, per_eps=0.01, per_abs_err_upper=1.0, td3=False, policy_delay=2,
+                 minimax=False, adv_eps=1e-3, adv_eps_s=1e-5):
         if td3 and world_size > 1:
             raise ValueError("--td3 runs on one GPU (MATD3 has no data-parallel variant)")
+        if minimax and world_size > 1:
+            raise ValueError("--minimax runs on one GPU (M3DDPG has no data-parallel variant)")
         sp = envs.spec(scenario, n_agents, scenario_adversaries)
         self.spec = sp
         n = sp.n_agents
@@ -61,7 +64,8 @@ class VecRunner:
                           seed=seed * 1000003 + 17, world_size=world_size, rank=rank, device=device,
                           episode_log_rows=episode_log_rows, prioritized=prioritized, per_alpha=per_alpha,
                           per_beta0=per_beta0, per_beta_inc=per_beta_inc, per_eps=per_eps,
-                          per_abs_err_upper=per_abs_err_upper, td3=td3, policy_delay=policy_delay)
+                          per_abs_err_upper=per_abs_err_upper, td3=td3, policy_delay=policy_delay,
+                          minimax=minimax, adv_eps=adv_eps, adv_eps_s=adv_eps_s)
         self.eng.init_params(seed)                           # identical replicas on every rank
         self.eng.seed_py_random(seed + rank)                 # per-rank index stream
         self.eng.env_reset()

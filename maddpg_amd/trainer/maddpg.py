@@ -20,6 +20,11 @@ returned list keeps its dtypes, with ``q_loss`` critic 1's, ``p_loss`` that of
 this agent's most recent actor step (0 before the first) and
 ``mean(target_q_next)`` the mean of the smaller target Q.
 
+With ``args.minimax`` (``--minimax``, ``args.adv_eps`` / ``args.adv_eps_s`` default
+1e-3 / 1e-5, sides from ``args.num_adversaries``) the session's engine is an
+M3DDPG one (``DESIGN.md`` section 20): ``p_loss`` and ``mean(target_q_next)`` are
+taken at the perturbed actions.
+
 ``model`` must be the reference's ``mlp_model`` (``train.py:39-46``: two
 hidden ReLU layers of ``args.num_units`` and a linear output, TF
 ``fully_connected`` with Xavier-uniform weights) -- the architecture the HIP

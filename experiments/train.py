@@ -110,6 +110,12 @@ def parse_args(argv=None):
                         help="--minimax: perturbation rate for agents on the other side of --num-adversaries")
     parser.add_argument("--adv-eps-s", type=float, default=1e-5,
                         help="--minimax: perturbation rate for agents on the same side")
+    parser.add_argument("--approx-policies", action="store_true", default=False,
+                        help="MADDPG with inferred policies: every agent learns approximators of the other agents' "
+                             "policies from replay and builds its TD target from them (strict mode, one GPU, npz "
+                             "checkpoints; not with --td3, --minimax or --prioritized-replay)")
+    parser.add_argument("--approx-lambda", type=float, default=1e-3,
+                        help="--approx-policies: weight of the approximators' entropy regulariser")
     # device-side policy evaluation (whole episodes in one launch; training state untouched)
     parser.add_argument("--evaluate", action="store_true", default=False,
                         help="load as --benchmark does and score the policies on evaluation episodes 0 .. "
@@ -396,10 +402,11 @@ def train(arglist):
     per = per_kwargs(arglist)
     td3_flags(arglist, world)
     minimax_flags(arglist, world)
+    approx_flags(arglist, world)
     try:
         runner = _make_runner(arglist, VecRunner, world, rank, per)
     except MdpError as e:      # e.g. prioritized replay with throughput mode or several GPUs
-        if not per and not arglist.td3 and not arglist.minimax:
+        if not per and not arglist.td3 and not arglist.minimax and not arglist.approx_policies:
             raise
         raise SystemExit(str(e))
     return _train(arglist, runner, exp_name, world, rank)
@@ -441,8 +448,31 @@ def minimax_flags(arglist, world=1):
         raise SystemExit("--minimax runs on one GPU (--num-gpus 1)")
 
 
+def approx_flags(arglist, world=1):
+    """--approx-policies is MADDPG with inferred policies on one GPU in strict mode:
+    refuse the combinations the library has no variant for before anything is built"""
+    if not getattr(arglist, "approx_policies", False):
+        return
+    lam = arglist.approx_lambda
+    if not (lam >= 0 and lam != float("inf")):
+        raise SystemExit("--approx-lambda must be finite and >= 0")
+    if arglist.prioritized_replay:
+        raise SystemExit("--approx-policies does not combine with --prioritized-replay")
+    if arglist.td3:
+        raise SystemExit("--approx-policies does not combine with --td3")
+    if arglist.minimax:
+        raise SystemExit("--approx-policies does not combine with --minimax")
+    if arglist.update_mode != "strict":
+        raise SystemExit("--approx-policies needs --update-mode strict")
+    if (arglist.num_gpus or 1) > 1 or world > 1:
+        raise SystemExit("--approx-policies runs on one GPU (--num-gpus 1)")
+    if getattr(arglist, "save_format", "npz") == "tf1":
+        raise SystemExit("--approx-policies saves npz checkpoints only (the approximators have no reference "
+                         "variable names)")
+
+
 def _make_runner(arglist, VecRunner, world, rank, per):
-    from maddpg_amd.common.tf_util import minimax_kwargs, td3_kwargs
+    from maddpg_amd.common.tf_util import approx_kwargs, minimax_kwargs, td3_kwargs
     runner = VecRunner(arglist.scenario, arglist.num_envs, n_agents=arglist.num_agents,
                        scenario_adversaries=arglist.scenario_adversaries,
                        num_adversaries=arglist.num_adversaries, good_policy=arglist.good_policy,
@@ -454,7 +484,7 @@ def _make_runner(arglist, VecRunner, world, rank, per):
                        capacity=arglist.buffer_size,
                        # the learning-curve windows of one terminal step span <= save_rate + E episodes
                        episode_log_rows=max(4096, 4 * arglist.num_envs, arglist.save_rate + 2 * arglist.num_envs),
-                       **per, **td3_kwargs(arglist), **minimax_kwargs(arglist))
+                       **per, **td3_kwargs(arglist), **minimax_kwargs(arglist), **approx_kwargs(arglist))
     if arglist.update_mode != "strict":
         runner.eng.set_update_mode(arglist.update_mode)
     return runner
@@ -518,6 +548,11 @@ def _train(arglist, runner, exp_name, world, rank):
             else:
                 print("steps: {}, episodes: {}, mean episode reward: {}, agent episode reward: {}, time: {}".format(
                     steps, length, mean_ep, mean_ag, round(time.time() - t_start, 3)), flush=True)
+            if arglist.approx_policies:
+                # the approximators' fit on a fresh draw of replay rows (the training index stream stays put)
+                aq = runner.eng.approx_quality()
+                print("approx: episodes: {}, pairs: {}, mean cross-entropy: {}, mean KL: {}".format(
+                    length, len(aq["pairs"]), aq["mean_ce"], aq["mean_kl"]), flush=True)
             t_start = time.time()
         if arglist.eval_episodes > 0 and rank == 0:
             # the same ids every time: checkpoints compared on identical start states
@@ -565,6 +600,7 @@ def main(argv=None):
     arglist = parse_args(argv)
     td3_flags(arglist)
     minimax_flags(arglist)
+    approx_flags(arglist)
     if arglist.num_gpus is not None:
         from maddpg_amd.launch import rank_launch_plan, run_ranks
         plan = rank_launch_plan(arglist.num_gpus, os.environ, os.path.abspath(__file__), argv,

@@ -301,8 +301,9 @@ int mdp_apply_grad(mdp_handle* h, int32_t agent, int32_t net, float scale);
 int mdp_get_stats(mdp_handle* h, int32_t agent, double out6[6]);
 /* debug check (the reference's _Function(check_nan), tf_util.py:322,366-368):
  * *nonfinite_out = the number of NaN / Inf values in every parameter set
- * (weights, targets, Adam m and v of every agent) and in the agents' update
- * stats; counted on the device, synchronous (ABI 5) */
+ * (weights, targets, Adam m and v of every agent; the second critic's after
+ * mdp_td3_enable, the approximators' after mdp_approx_enable) and in the agents'
+ * update stats; counted on the device, synchronous (ABI 5) */
 int mdp_check_finite(mdp_handle* h, int64_t* nonfinite_out);
 
 /* ---- update mode of the round paths (mdp_update_round, mdp_train_step) ----
@@ -625,6 +626,62 @@ int mdp_minimax_info(mdp_handle* h, float* eps_out_host);
  * actor steps of a minimax agent reads it (the agent's own slot unperturbed) */
 int mdp_minimax_debug_adv(mdp_handle* h, float* critic_adv_dev, float* actor_adv_dev);
 
+/* ---- Inferred policies: approximators of the other agents, trained on the ----
+ * device (Lowe et al. 2017, section 4.2).  Every agent i
+ * with a MADDPG critic gets, for every other agent j, an approximator phi_i^j:
+ * an MLP of agent j's actor shape (pad rules and action width A_j included)
+ * with its own target network, Adam slots and beta powers, in a caller-
+ * allocated device buffer of mdp_approx_bytes bytes that must outlive the
+ * handle.  Agents with a local (DDPG) critic get none; their update is today's,
+ * bit for bit.  Agent i's update on its minibatch then runs
+ *   1. the critic step, with the target action of every j != i drawn from the
+ *      target approximator of (i, j) on o'_j instead of target actor j -- same
+ *      noise (u_tgt[j] or Philox stream (i << 8) | (j + 1)); agent i's own
+ *      target action still comes from its target actor;
+ *   2. the actor step and Polyak of actor and critic, unchanged;
+ *   3. one gradient step of every phi_i^j on the same rows:
+ *        loss = mean_b[ -sum_c a_c log p_c - lambda H(p) ],  p = softmax of the
+ *        first A_j logits of phi_i^j(o_j), a = agent j's replayed action, log p
+ *        the log-softmax; per-tensor clip and Adam with the handle's lr, betas,
+ *        eps and clip on the pair's own slots; then target <- (1 - tau) target +
+ *        tau phi with the optimizer kernels' constants.
+ * With every target approximator holding the bits of the target actor it
+ * stands for, agent i's first update equals the MADDPG update of the general
+ * gradient kernels bit for bit.  The training-noise counter advances as without
+ * the option.  lambda is finite and >= 0 (the paper: 1e-3).  Enable comes before
+ * the handle's first update / train call and zeroes the buffer: write the
+ * approximators afterwards.  Runs in strict mode on one GPU on the general
+ * gradient kernels; refused: prioritized replay, MATD3, M3DDPG, throughput
+ * mode, mdp_update_all, data parallelism and the phase entry points.
+ * The buffer starts with, per observing agent, five param-space regions (net,
+ * target, Adam m, Adam v, reduced gradient: param_floats floats each, rounded
+ * up to 256 bytes): phi_i^j lies in agent j's actor span at the arena's
+ * offsets, every other span stays zero; the partials, records, beta powers and
+ * the optimizer launches' own sync area follow. */
+enum mdp_approx_set { MDP_APX_NET = 0, MDP_APX_TARGET = 1, MDP_APX_M = 2, MDP_APX_V = 3, MDP_APX_GRAD = 4 };
+int64_t mdp_approx_bytes(const mdp_config* cfg);
+int mdp_approx_enable(mdp_handle* h, void* buf_dev, int64_t bytes, float lambda);
+/* set `which` (mdp_approx_set) of phi_observer^agent in agent's actor layout, as
+ * mdp_set_params / mdp_get_params take MDP_ACTOR.  MDP_APX_GRAD reads the raw
+ * (unclipped) batch gradient of the pair's last gradient launch */
+int mdp_approx_set_params(mdp_handle* h, int32_t observer, int32_t agent, int32_t which, const float* src, int64_t n);
+int mdp_approx_get_params(mdp_handle* h, int32_t observer, int32_t agent, int32_t which, float* dst, int64_t n);
+int mdp_approx_get_beta_powers(mdp_handle* h, int32_t observer, int32_t agent, float out2[2]);
+int mdp_approx_set_beta_powers(mdp_handle* h, int32_t observer, int32_t agent, const float in2[2]);
+/* out4 = {cross-entropy, entropy, loss = cross-entropy - lambda entropy (batch
+ * means of the pair's last gradient launch), steps of the pair so far}; synchronises */
+int mdp_approx_info(mdp_handle* h, int32_t observer, int32_t agent, double out4[4]);
+/* mdp_actor_logits on phi_observer^agent (target != 0: its target network); the
+ * trailing arguments keep mdp_actor_logits' order: obs_dev, logits_dev, rows */
+int mdp_approx_logits(mdp_handle* h, int32_t observer, int32_t agent, int32_t target, const float* obs_dev,
+                      float* logits_dev, int32_t rows);
+/* step 3 alone on rows idx_dev [batch_size]: mdp_approx_grad launches only the
+ * gradient kernel of every pair of `observer`; mdp_approx_step the whole step
+ * (gradients, every pair's optimizer step, Polyak).  Neither touches a MADDPG
+ * parameter set or the noise counter */
+int mdp_approx_grad(mdp_handle* h, int32_t observer, const int32_t* idx_dev);
+int mdp_approx_step(mdp_handle* h, int32_t observer, const int32_t* idx_dev);
+
 /* ---- profiling: HIP events bracketing every launch of one kernel kind -- */
 enum mdp_kernel_kind {
     MDP_K_INDEX = 0, MDP_K_GATHER = 1, MDP_K_CRITIC_GRAD = 2, MDP_K_ACTOR_GRAD = 3,
@@ -634,6 +691,11 @@ enum mdp_kernel_kind {
     MDP_K_EVAL = 12,       /* k_eval_episodes (mdp_evaluate, mdp_evaluate_matchups, mdp_evaluate_q + its k_eval_returns) */
     MDP_K_COUNT = 13
 };
+/* Inferred policies add no kind: k_approx_grad is timed under MDP_K_ACTOR_GRAD,
+ * the pairs' optimizer launches under MDP_K_REDUCE_APPLY (or MDP_K_REDUCE and
+ * MDP_K_APPLY) and the approximators' k_polyak under MDP_K_APPLY.  With the
+ * option on, those kinds therefore sum two different kernels each: time one of
+ * them alone through mdp_approx_grad / mdp_approx_step or with device events. */
 int mdp_prof_enable(mdp_handle* h, int32_t kind, int32_t on);
 /* which grad kernels serve `agent`: 1 = register-resident k_*_grad_r (H = 64
  * envelope), 0 = general k_*_grad */

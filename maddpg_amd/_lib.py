@@ -30,6 +30,8 @@ WHICH = {"actor": 0, "critic": 1, "tgt_actor": 2, "tgt_critic": 3, "m_actor": 4,
          "m_critic": 6, "v_critic": 7, "g_actor": 8, "g_critic": 9,
          # MATD3 (mdp_td3_enable): the second critic's sets
          "critic2": 10, "tgt_critic2": 11, "m_critic2": 12, "v_critic2": 13, "g_critic2": 14}
+# inferred policies (mdp_approx_enable): the sets of one approximator (mdp_approx_set)
+APX_WHICH = {"net": 0, "tgt": 1, "m": 2, "v": 3, "grad": 4}
 REGION = {"theta": 0, "target": 1, "adam_m": 2, "adam_v": 3, "grad": 4, "replay": 5, "index": 6,
           "stats": 7, "env": 8, "eplog": 9, "beta": 10, "slab": 11, "ctl": 12}
 KERNEL = {"index": 0, "gather": 1, "critic_grad": 2, "actor_grad": 3, "apply": 4, "rollout": 5,
@@ -180,6 +182,16 @@ SIGNATURES = {
     "mdp_minimax_enable": (ctypes.c_int, [_P, _F32P]),
     "mdp_minimax_info": (ctypes.c_int, [_P, _F32P]),
     "mdp_minimax_debug_adv": (ctypes.c_int, [_P, _P, _P]),
+    "mdp_approx_bytes": (_I64, [ctypes.POINTER(MdpConfig)]),
+    "mdp_approx_enable": (ctypes.c_int, [_P, _P, _I64, ctypes.c_float]),
+    "mdp_approx_set_params": (ctypes.c_int, [_P, _I32, _I32, _I32, _F32P, _I64]),
+    "mdp_approx_get_params": (ctypes.c_int, [_P, _I32, _I32, _I32, _F32P, _I64]),
+    "mdp_approx_get_beta_powers": (ctypes.c_int, [_P, _I32, _I32, _F32P]),
+    "mdp_approx_set_beta_powers": (ctypes.c_int, [_P, _I32, _I32, _F32P]),
+    "mdp_approx_info": (ctypes.c_int, [_P, _I32, _I32, _F64P]),
+    "mdp_approx_logits": (ctypes.c_int, [_P, _I32, _I32, _I32, _P, _P, _I32]),
+    "mdp_approx_grad": (ctypes.c_int, [_P, _I32, _P]),
+    "mdp_approx_step": (ctypes.c_int, [_P, _I32, _P]),
     "mdp_prof_enable": (ctypes.c_int, [_P, _I32, _I32]),
     "mdp_prof_read": (ctypes.c_int, [_P, _I32, _F64P, ctypes.POINTER(_I64)]),
 }

@@ -72,7 +72,7 @@ class Session:
                               max_episode_len=args.max_episode_len, capacity=int(1e6), lr=args.lr,
                               gamma=args.gamma, seed=seed, act_dims=t0.act_dims,
                               num_adversaries=int(getattr(args, "num_adversaries", 0) or 0), **per_kwargs(args),
-                              **td3_kwargs(args), **minimax_kwargs(args))
+                              **td3_kwargs(args), **minimax_kwargs(args), **approx_kwargs(args))
         self._engine.init_params(seed)
         return self._engine
 
@@ -163,6 +163,13 @@ def minimax_kwargs(args):
     if not getattr(args, "minimax", False):
         return {}
     return dict(minimax=True, adv_eps=getattr(args, "adv_eps", 1e-3), adv_eps_s=getattr(args, "adv_eps_s", 1e-5))
+
+
+def approx_kwargs(args):
+    """Engine keywords of --approx-policies / --approx-lambda (experiments/train.py); {} when off"""
+    if not getattr(args, "approx_policies", False):
+        return {}
+    return dict(approx=True, approx_lambda=getattr(args, "approx_lambda", 1e-3))
 
 
 def per_kwargs(args):

@@ -428,6 +428,20 @@ struct mdp_handle {
   bool minimax = false;
   float mm_eps[MDP_MAX_AGENTS][MDP_MAX_AGENTS] = {};
   float *mm_adv_c = nullptr, *mm_adv_a = nullptr;
+  // inferred policies (mdp_approx_enable): the caller's buffer -- per observing
+  // agent five param-space regions (net, target, m, v, grad), then the shared
+  // partials, the records [n][n][nwg][8], beta powers [n][n][4] and the
+  // optimizer launches' own sync area (one slot per approximated agent)
+  bool approx = false;
+  float apx_lambda = 1e-3f;
+  char* apx_buf = nullptr;
+  int64_t apx_region = 0, apx_obs_stride = 0;  // bytes
+  float *apx_slab = nullptr, *apx_beta = nullptr;
+  double* apx_stat = nullptr;
+  uint32_t *apx_ticket = nullptr, *apx_ctr = nullptr;
+  uint64_t* apx_part = nullptr;
+  int64_t apx_count[MDP_MAX_AGENTS] = {};  // approximator steps of observer i so far
+  int apx_pending = -1;  // observer whose gradient-only launch (mdp_approx_grad) the partials hold, or -1
 };
 
 namespace {
@@ -759,6 +773,15 @@ bool mm_agent(const mdp_handle* h, int agent) {
   return h->minimax && !h->L.topo.ag[agent].local_q && h->cfg.n_agents > 1;
 }
 
+// inferred policies: agent has approximators -- a MADDPG critic and someone to approximate
+bool apx_agent(const mdp_handle* h, int agent) {
+  return h->approx && !h->L.topo.ag[agent].local_q && h->cfg.n_agents > 1;
+}
+// param-space base of set k (mdp_approx_set) of observer's approximators
+float* apx_base(const mdp_handle* h, int observer, int k) {
+  return (float*)(h->apx_buf + observer * h->apx_obs_stride + k * h->apx_region);
+}
+
 int do_critic_grad(mdp_handle* h, int agent, const int32_t* idx, const float* u_tgt, int32_t* pf_out = nullptr,
                    bool tp = false, bool apre = false, const float* u_act = nullptr, int post_prev = -1,
                    int pf_n = 0, bool shared = false) {
@@ -789,6 +812,13 @@ int do_critic_grad(mdp_handle* h, int agent, const int32_t* idx, const float* u_
     return 0;
   }
   if (lds_critic_bytes(h->L.topo, a.group) > MDP_LDS_BUDGET) return fail(h, "critic step does not fit in LDS");
+  if (apx_agent(h, agent) && !tp) {  // the others' target actions from this agent's target approximators
+    CriticArgsApx x;
+    static_cast<CriticArgs&>(x) = a;
+    x.apx_target = apx_base(h, agent, MDP_APX_TARGET);
+    HIPCHK(h, mdp_launch_critic_grad_apx(x, h->L.topo.H, lds_critic_bytes(h->L.topo, a.group), h->stream));
+    return 0;
+  }
   if (h->per && !tp)
     HIPCHK(h, mdp_launch_critic_grad_per(per_critic_args(h, a), h->L.topo.H, lds_critic_bytes(h->L.topo, a.group),
                                          h->stream));
@@ -1207,6 +1237,106 @@ int do_update_td3(mdp_handle* h, int agent, const int32_t* idx, const float* u_t
   return 0;
 }
 
+// ---- inferred policies
+// the raw gradients of every approximator of `observer` on rows idx: one launch
+int do_approx_grad(mdp_handle* h, int observer, const int32_t* idx) {
+  ApproxArgs a;
+  a.B = h->cfg.batch_size;
+  a.nwg = h->L.nwg;
+  a.m = 0;
+  for (int j = 0; j < MDP_MAX_AGENTS; ++j) a.agents[j] = 0;
+  for (int j = 0; j < h->cfg.n_agents; ++j)
+    if (j != observer) a.agents[a.m++] = j;
+  a.phi = apx_base(h, observer, MDP_APX_NET);
+  a.replay = h->replay;
+  a.idx = idx;
+  a.inv_b = 1.0f / (float)a.B;
+  a.lambda = h->apx_lambda;
+  a.slab = h->apx_slab;
+  a.slab_stride = h->L.slab_a;
+  a.slab_stat = h->apx_stat + (int64_t)observer * h->cfg.n_agents * h->L.nwg * 8;
+  a.topo = h->L.topo;
+  ProfScope p(h, MDP_K_ACTOR_GRAD);
+  HIPCHK(h, mdp_launch_approx_grad(a, h->L.topo.H, lds_approx_bytes(h->L.topo), h->stream));
+  return 0;
+}
+
+// the optimizer step of phi_observer^j (pair p of the launch above): agent j's
+// actor step with every pointer in the approximator buffer, no Polyak, no stats
+FusedApplyArgs apx_fused_args(mdp_handle* h, int observer, int j, int p) {
+  FusedApplyArgs f = fused_args_for(h, j, 0);
+  ApplyArgs& a = f.ap;
+  a.theta = apx_base(h, observer, MDP_APX_NET);
+  a.target = apx_base(h, observer, MDP_APX_TARGET);
+  a.m = apx_base(h, observer, MDP_APX_M);
+  a.v = apx_base(h, observer, MDP_APX_V);
+  a.grad = apx_base(h, observer, MDP_APX_GRAD);
+  a.slab = h->apx_slab + (int64_t)p * h->L.nwg * h->L.slab_a;
+  a.beta = h->apx_beta + ((int64_t)observer * h->cfg.n_agents + j) * 4;
+  a.polyak = 0;
+  a.stats_mode = 0;
+  a.slab_stat = nullptr;
+  a.y = nullptr;
+  a.stats_out = nullptr;
+  a.ticket = h->apx_ticket;
+  a.bump_ctr = 0;
+  f.sync_ctr = h->apx_ctr + (int64_t)j * 8 * 32;
+  f.done_ctr = f.sync_ctr + 6 * 32;
+  f.sync_part = h->apx_part + (int64_t)j * 6 * MDP_RA_MAXCH * 2;
+  return f;
+}
+
+int apx_reduce(mdp_handle* h, int observer, int j, int p, float* beta) {
+  const NDesc& d = net_of(h, j, 0);
+  ReduceArgs r;
+  r.slab = h->apx_slab + (int64_t)p * h->L.nwg * h->L.slab_a;
+  r.nwg = h->L.nwg;
+  r.slab_stride = h->L.slab_a;
+  r.grad = apx_base(h, observer, MDP_APX_GRAD);
+  r.off = d.off;
+  r.size = d.size;
+  r.beta = beta;
+  r.b1 = h->cfg.adam_b1;
+  r.b2 = h->cfg.adam_b2;
+  r.ctl = h->ctl;
+  r.bump_ctr = 0;
+  ProfScope ps(h, MDP_K_REDUCE);
+  HIPCHK(h, mdp_launch_reduce(r, h->stream));
+  return 0;
+}
+
+// every pair's clip + Adam, then Polyak of the observer's whole target region
+// (the spans without an approximator hold zeros and stay zeros)
+int do_approx_opt(mdp_handle* h, int observer) {
+  int p = 0;
+  for (int j = 0; j < h->cfg.n_agents; ++j) {
+    if (j == observer) continue;
+    const FusedApplyArgs f = apx_fused_args(h, observer, j, p);
+    if (h->fused_apply && reduce_apply_ok(h, j, 0)) {
+      ProfScope ps(h, MDP_K_REDUCE_APPLY);
+      HIPCHK(h, mdp_launch_reduce_apply(f, h->stream));
+    } else {
+      int rc;
+      if ((rc = apx_reduce(h, observer, j, p, f.ap.beta))) return rc;
+      ApplyArgs a = f.ap;
+      a.slab = nullptr;
+      ProfScope ps(h, MDP_K_APPLY);
+      HIPCHK(h, mdp_launch_apply(a, h->stream));
+    }
+    ++p;
+  }
+  const ApplyArgs a = apply_args(h, observer, 0, 1.0f);
+  ProfScope ps(h, MDP_K_APPLY);
+  HIPCHK(h, mdp_launch_polyak(apx_base(h, observer, MDP_APX_TARGET), apx_base(h, observer, MDP_APX_NET), h->L.PT, a.pa,
+                              a.pb, h->ctl, h->stream));
+  return 0;
+}
+
+int do_approx_step(mdp_handle* h, int observer, const int32_t* idx) {
+  const int rc = do_approx_grad(h, observer, idx);
+  return rc ? rc : do_approx_opt(h, observer);
+}
+
 // pf_out: the critic kernel also draws the next round's indices there (fast path only)
 // post_prev >= 0: this critic step finishes the work that agent post_prev's
 // actor launch started (critic_post); pre_next >= 0: this actor launch starts
@@ -1235,6 +1365,9 @@ int do_update(mdp_handle* h, int agent, const int32_t* idx, const float* u_tgt, 
     if ((rc = do_reduce(h, agent, 0))) return rc;
     if ((rc = do_apply(h, agent, 0, false, 1.0f))) return rc;
   }
+  // inferred policies: the approximators step last, so every target this update
+  // read was the one standing at its start
+  if (apx_agent(h, agent)) return do_approx_step(h, agent, idx);
   return 0;
 }
 
@@ -1662,6 +1795,33 @@ Td3Layout td3_layout(const mdp_config& c, const Layout& L) {
   t.stats = take(8 * 8 * (int64_t)c.n_agents);
   t.ticket = take(256);
   t.ctr = take((int64_t)MDP_MAX_AGENTS * 8 * 128);          // per agent 8 counters x 128 B (mdp_ra_sync_bytes)
+  t.part = take((int64_t)MDP_MAX_AGENTS * 6 * MDP_RA_MAXCH * 16);
+  t.total = o;
+  return t;
+}
+
+const char* kApxNoDp = "inferred policies (mdp_approx_enable) run on one GPU in strict mode: no data-parallel exchange";
+
+// byte offsets inside the caller's approximator buffer
+struct ApxLayout {
+  int64_t region, obs_stride, slab, stat, beta, ticket, ctr, part, total;
+};
+ApxLayout apx_layout(const mdp_config& c, const Layout& L) {
+  ApxLayout t;
+  const int64_t n = c.n_agents;
+  t.region = a256(4 * L.PT);
+  t.obs_stride = 5 * t.region;
+  int64_t o = n * t.obs_stride;
+  auto take = [&](int64_t bytes) {
+    const int64_t at = o;
+    o += a256(bytes);
+    return at;
+  };
+  t.slab = take(4 * std::max<int64_t>(n - 1, 1) * L.nwg * L.slab_a);
+  t.stat = take(8 * 8 * n * n * L.nwg);
+  t.beta = take(4 * 4 * n * n);
+  t.ticket = take(256);
+  t.ctr = take((int64_t)MDP_MAX_AGENTS * 8 * 128);  // per approximated agent 8 counters x 128 B
   t.part = take((int64_t)MDP_MAX_AGENTS * 6 * MDP_RA_MAXCH * 16);
   t.total = o;
   return t;
@@ -2149,11 +2309,18 @@ int mdp_q_values(mdp_handle* h, int32_t agent, int32_t target, const float* x_de
 
 // ---------------------------------------------------------------- training
 // MATD3's host counters: the launches about to be issued or captured count from
-// the committed state; td3_commit after they (or a graph replay of them) went out
+// the committed state; commit_rounds after they (or a graph replay of them) went out
 static void td3_begin(mdp_handle* h) {
   for (int i = 0; i < MDP_MAX_AGENTS; ++i) h->td3_work[i] = h->td3_count[i];
 }
-static void td3_commit(mdp_handle* h, int rounds) {
+// the host-side counts of `rounds` whole rounds that went out: the approximators'
+// step counts (inferred policies) and MATD3's update counts; a plain handle has neither
+static void commit_rounds(mdp_handle* h, int rounds) {
+  if (h->approx && rounds > 0) {  // inferred policies: every observer's pairs stepped once per round
+    for (int i = 0; i < h->cfg.n_agents; ++i)
+      if (apx_agent(h, i)) h->apx_count[i] += rounds;
+    h->apx_pending = -1;
+  }
   if (!h->td3) return;
   for (int i = 0; i < h->cfg.n_agents; ++i) h->td3_count[i] += rounds;
 }
@@ -2228,6 +2395,10 @@ int mdp_update(mdp_handle* h, int32_t agent, const int32_t* idx_dev, const float
   td3_begin(h);
   const int rc = do_update(h, agent, idx, u_tgt_dev, u_act_dev);
   if (!rc && h->td3) h->td3_count[agent] += 1;
+  if (!rc && apx_agent(h, agent)) {
+    h->apx_count[agent] += 1;
+    h->apx_pending = -1;
+  }
   return rc;
 }
 
@@ -2372,7 +2543,7 @@ int mdp_update_round(mdp_handle* h) {
     ++h->eager_rounds;  // the first round runs eagerly (one-time kernel attribute setup)
     td3_begin(h);
     const int rc = round_launches(h);
-    if (!rc) td3_commit(h, 1);
+    if (!rc) commit_rounds(h, 1);
     return rc;
   }
   if (h->td3) {
@@ -2380,7 +2551,7 @@ int mdp_update_round(mdp_handle* h) {
     const int rc = td3_graph(h, td3_key(h, 0, {}), [&] { return round_launches(h); }, &x);
     if (rc) return rc;
     HIPCHK(h, hipGraphLaunch(x, h->stream));
-    td3_commit(h, 1);
+    commit_rounds(h, 1);
     return 0;
   }
   if (!h->round_exec) {
@@ -2399,6 +2570,7 @@ int mdp_update_round(mdp_handle* h) {
     HIPCHK(h, hipGraphInstantiate(&h->round_exec, g, nullptr, nullptr, 0));
   }
   HIPCHK(h, hipGraphLaunch(h->round_exec, h->stream));
+  commit_rounds(h, 1);  // (the approximators' step counts; MATD3 returned above)
   return 0;
 }
 
@@ -2420,6 +2592,7 @@ int mdp_dp_init(mdp_handle* h, const uint8_t* id128, int32_t world, int32_t rank
   if (h->per) return fail(h, kPerNoDp);
   if (h->td3) return fail(h, (std::string("mdp_dp_init: ") + kTd3NoDp).c_str());
   if (h->minimax) return fail(h, (std::string("mdp_dp_init: ") + kMmNoDp).c_str());
+  if (h->approx) return fail(h, (std::string("mdp_dp_init: ") + kApxNoDp).c_str());
   if (h->update_mode != 0) return fail(h, "join data parallelism before choosing the throughput mode");
   if (h->p2p || h->xbuf) return fail(h, "mdp_dp_init: the xGMI exchange is already set up");
   if (!rccl().ok) return fail(h, "librccl.so.1 could not be loaded");
@@ -2460,6 +2633,7 @@ int mdp_dp_xgmi_open(mdp_handle* h, int32_t world, int32_t rank, uint8_t* handle
   if (h->per) return fail(h, kPerNoDp);
   if (h->td3) return fail(h, (std::string("mdp_dp_xgmi_open: ") + kTd3NoDp).c_str());
   if (h->minimax) return fail(h, (std::string("mdp_dp_xgmi_open: ") + kMmNoDp).c_str());
+  if (h->approx) return fail(h, (std::string("mdp_dp_xgmi_open: ") + kApxNoDp).c_str());
   if (h->update_mode != 0) return fail(h, "join data parallelism before choosing the throughput mode");
   if (h->comm) return fail(h, "mdp_dp_xgmi_open: an RCCL communicator is already set up");
   if (h->xbuf) return fail(h, "mdp_dp_xgmi_open: already open");
@@ -2532,6 +2706,8 @@ int mdp_dp_xgmi_probe(mdp_handle* h, int32_t* mismatches) {
 
 int mdp_dp_xgmi_enable(mdp_handle* h) {
   if (unusable(h)) return -1;
+  // (an approx handle never gets past mdp_dp_xgmi_open, so say why before "not connected")
+  if (h->approx) return fail(h, (std::string("mdp_dp_xgmi_enable: ") + kApxNoDp).c_str());
   if (!h->xd_dev) return fail(h, "mdp_dp_xgmi_enable: not connected");
   if (h->per) return fail(h, kPerNoDp);
   if (h->td3) return fail(h, (std::string("mdp_dp_xgmi_enable: ") + kTd3NoDp).c_str());
@@ -2628,6 +2804,9 @@ int mdp_set_update_mode(mdp_handle* h, int32_t mode) {
     if (h->td3) return fail(h, "mdp_set_update_mode: mode 1 (throughput) is not supported with MATD3 (mdp_td3_enable)");
     if (h->minimax)
       return fail(h, "mdp_set_update_mode: mode 1 (throughput) is not supported with M3DDPG (mdp_minimax_enable)");
+    if (h->approx)
+      return fail(h, "mdp_set_update_mode: mode 1 (throughput) is not supported with inferred policies "
+                     "(mdp_approx_enable)");
     if (h->per) return fail(h, "prioritized replay needs the strict update mode (throughput mode is not supported)");
     if (!tp_ok(h)) return fail(h, "throughput mode needs the fused optimizer step for every net and <= 8 agents");
     HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -2645,6 +2824,8 @@ int mdp_update_all(mdp_handle* h, const int32_t* idx_dev, const float* u_tgt_dev
   if (unusable(h)) return -1;
   if (h->td3) return fail(h, "mdp_update_all: throughput mode is not supported with MATD3 (mdp_td3_enable)");
   if (h->minimax) return fail(h, "mdp_update_all: throughput mode is not supported with M3DDPG (mdp_minimax_enable)");
+  if (h->approx)
+    return fail(h, "mdp_update_all: throughput mode is not supported with inferred policies (mdp_approx_enable)");
   if (h->update_mode != 1) return fail(h, "mdp_update_all: set throughput mode first");
   h->trained = true;
   if (h->len <= 0) return fail(h, "update on an empty replay buffer");
@@ -2681,6 +2862,9 @@ int mdp_critic_grad(mdp_handle* h, int32_t agent, const int32_t* idx_dev, const 
   if (h->per) return fail(h, "mdp_critic_grad: the phase entry points serve data parallelism; prioritized replay uses mdp_update");
   if (h->td3) return fail(h, kTd3NoPhase("mdp_critic_grad"));
   if (h->minimax) return fail(h, kMmNoPhase("mdp_critic_grad"));
+  if (h->approx)
+    return fail(h, "mdp_critic_grad: the phase entry points serve data parallelism; inferred policies (mdp_approx_enable) use "
+                   "mdp_update");
   h->trained = true;
   MDP_DEV(h, idx_dev, 4 * (int64_t)h->cfg.batch_size, "mdp_critic_grad", false);
   MDP_DEV(h, u_tgt_dev, 4 * (int64_t)h->cfg.n_agents * h->cfg.batch_size * MDP_ACT_DIM, "mdp_critic_grad", true);
@@ -2692,6 +2876,9 @@ int mdp_actor_grad(mdp_handle* h, int32_t agent, const int32_t* idx_dev, const f
   if (!idx_dev) return fail(h, "actor_grad needs indices");
   if (h->td3) return fail(h, kTd3NoPhase("mdp_actor_grad"));
   if (h->minimax) return fail(h, kMmNoPhase("mdp_actor_grad"));
+  if (h->approx)
+    return fail(h, "mdp_actor_grad: the phase entry points serve data parallelism; inferred policies (mdp_approx_enable) use "
+                   "mdp_update");
   h->started = true;
   MDP_DEV(h, idx_dev, 4 * (int64_t)h->cfg.batch_size, "mdp_actor_grad", false);
   MDP_DEV(h, u_act_dev, 4 * (int64_t)h->cfg.batch_size * MDP_ACT_DIM, "mdp_actor_grad", true);
@@ -2702,6 +2889,9 @@ int mdp_reduce_grad(mdp_handle* h, int32_t agent, int32_t net) {
   if (bad_agent(h, agent)) return -1;
   if (h->td3) return fail(h, kTd3NoPhase("mdp_reduce_grad"));
   if (h->minimax) return fail(h, kMmNoPhase("mdp_reduce_grad"));
+  if (h->approx)
+    return fail(h, "mdp_reduce_grad: the phase entry points serve data parallelism; inferred policies (mdp_approx_enable) use "
+                   "mdp_update");
   return do_reduce(h, agent, net ? 1 : 0);
 }
 
@@ -2709,6 +2899,9 @@ int mdp_apply_grad(mdp_handle* h, int32_t agent, int32_t net, float scale) {
   if (bad_agent(h, agent)) return -1;
   if (h->td3) return fail(h, kTd3NoPhase("mdp_apply_grad"));
   if (h->minimax) return fail(h, kMmNoPhase("mdp_apply_grad"));
+  if (h->approx)
+    return fail(h, "mdp_apply_grad: the phase entry points serve data parallelism; inferred policies (mdp_approx_enable) use "
+                   "mdp_update");
   return do_apply(h, agent, net ? 1 : 0, false, scale);
 }
 
@@ -3110,7 +3303,7 @@ static int step_launches(mdp_handle* h, int rounds) {
     for (int r = 0; r < rounds && !rc; ++r) rc = per_round_launches(h, r == 0);
     return rc;
   }
-  if (h->td3 || h->minimax) {  // MATD3, M3DDPG: one n B draw per round, no draw rides on another launch
+  if (h->td3 || h->minimax || h->approx) {  // MATD3, M3DDPG, inferred policies: one n B draw per round, none rides on another launch
     int rc = env_step_launch(h, nullptr, nullptr);
     for (int r = 0; r < rounds && !rc; ++r) {
       if ((rc = launch_make_index(h, nb, h->index))) break;
@@ -3155,7 +3348,7 @@ static int train_step_body(mdp_handle* h, int rounds) {
     if (rounds > 0) ++h->eager_steps;  // first training step eager (one-time kernel attribute setup)
     td3_begin(h);
     const int rc = step_launches(h, rounds);
-    if (!rc) td3_commit(h, rounds);
+    if (!rc) commit_rounds(h, rounds);
     return rc;
   }
   if (h->td3) {
@@ -3163,7 +3356,7 @@ static int train_step_body(mdp_handle* h, int rounds) {
     const int rc = td3_graph(h, td3_key(h, 1, {rounds}), [&] { return step_launches(h, rounds); }, &x);
     if (rc) return rc;
     HIPCHK(h, hipGraphLaunch(x, h->stream));
-    td3_commit(h, rounds);
+    commit_rounds(h, rounds);
     return 0;
   }
   auto it = h->step_exec.find(rounds);
@@ -3186,6 +3379,7 @@ static int train_step_body(mdp_handle* h, int rounds) {
     it = h->step_exec.emplace(rounds, x).first;
   }
   HIPCHK(h, hipGraphLaunch(it->second, h->stream));
+  commit_rounds(h, rounds);  // (the approximators' step counts; MATD3 returned above)
   return 0;
 }
 
@@ -3277,7 +3471,7 @@ int mdp_train_steps(mdp_handle* h, int32_t n, const int32_t* rounds, int32_t lau
   } else {
     int total = 0;
     for (int k : ks) total += k;
-    td3_commit(h, total);
+    commit_rounds(h, total);
   }
   return rc;
 }
@@ -3383,6 +3577,11 @@ int mdp_check_finite(mdp_handle* h, int64_t* nonfinite) {
     const float* twin[4] = {h->theta2, h->target2, h->m2, h->v2};
     for (const float* p : twin) HIPCHK(h, mdp_launch_count_nonfinite(p, h->L.PT, &h->ctl->nonfinite, h->stream));
   }
+  if (h->approx) {  // every observer's approximator sets (the spans without one stay zero)
+    for (int i = 0; i < h->cfg.n_agents; ++i)
+      for (int k = MDP_APX_NET; k <= MDP_APX_V; ++k)
+        HIPCHK(h, mdp_launch_count_nonfinite(apx_base(h, i, k), h->L.PT, &h->ctl->nonfinite, h->stream));
+  }
   uint32_t c = 0;
   const int n = h->cfg.n_agents;
   std::vector<double> st(8 * (size_t)n);
@@ -3433,6 +3632,8 @@ int mdp_per_enable(mdp_handle* h, void* buf_dev, int64_t bytes, float alpha, flo
   if (h->per) return fail(h, "mdp_per_enable: already enabled");
   if (h->td3) return fail(h, "mdp_per_enable: prioritized replay and MATD3 (mdp_td3_enable) do not combine");
   if (h->minimax) return fail(h, "mdp_per_enable: prioritized replay and M3DDPG (mdp_minimax_enable) do not combine");
+  if (h->approx)
+    return fail(h, "mdp_per_enable: prioritized replay and inferred policies (mdp_approx_enable) do not combine");
   if (h->trained)
     return fail(h, "mdp_per_enable: call it before the handle's first update or train call");
   if (h->update_mode != 0)
@@ -3493,6 +3694,7 @@ int mdp_td3_enable(mdp_handle* h, void* buf_dev, int64_t bytes, int32_t policy_d
   if (policy_delay < 1 || policy_delay > 8) return fail(h, "mdp_td3_enable: policy_delay must be in 1..8");
   if (h->per) return fail(h, "mdp_td3_enable: MATD3 and prioritized replay (mdp_per_enable) do not combine");
   if (h->minimax) return fail(h, "mdp_td3_enable: MATD3 and M3DDPG (mdp_minimax_enable) do not combine");
+  if (h->approx) return fail(h, "mdp_td3_enable: MATD3 and inferred policies (mdp_approx_enable) do not combine");
   if (h->update_mode != 0)
     return fail(h, "mdp_td3_enable: MATD3 needs the strict update mode (throughput mode is not supported)");
   if (h->comm || h->p2p || h->xbuf || h->cfg.world_size > 1)
@@ -3561,6 +3763,8 @@ int mdp_minimax_enable(mdp_handle* h, const float* eps_host) {
       return fail(h, "mdp_minimax_enable: eps_host must hold finite values >= 0");
   if (h->per) return fail(h, "mdp_minimax_enable: M3DDPG and prioritized replay (mdp_per_enable) do not combine");
   if (h->td3) return fail(h, "mdp_minimax_enable: M3DDPG and MATD3 (mdp_td3_enable) do not combine");
+  if (h->approx)
+    return fail(h, "mdp_minimax_enable: M3DDPG and inferred policies (mdp_approx_enable) do not combine");
   if (h->update_mode != 0)
     return fail(h, "mdp_minimax_enable: M3DDPG needs the strict update mode (throughput mode is not supported)");
   if (h->comm || h->p2p || h->xbuf || h->cfg.world_size > 1)
@@ -3604,6 +3808,210 @@ int mdp_minimax_debug_adv(mdp_handle* h, float* critic_adv_dev, float* actor_adv
   h->mm_adv_a = actor_adv_dev;
   drop_graphs(h);  // the pointers are kernel arguments of the captured launches
   return 0;
+}
+
+// ------------------------------------------------------- inferred policies
+int64_t mdp_approx_bytes(const mdp_config* cfg) {
+  Layout L;
+  std::string err;
+  if (!cfg || !build_layout(cfg, L, err)) return -1;
+  return apx_layout(*cfg, L).total;
+}
+
+int mdp_approx_enable(mdp_handle* h, void* buf_dev, int64_t bytes, float lambda) {
+  MDP_NEED(h);
+  if (h->approx) return fail(h, "mdp_approx_enable: already enabled");
+  if (h->trained)
+    return fail(h, "mdp_approx_enable: call it before the handle's first update, round or train call");
+  if (!std::isfinite(lambda) || lambda < 0.f) return fail(h, "mdp_approx_enable: lambda must be finite and >= 0");
+  if (h->per)
+    return fail(h, "mdp_approx_enable: inferred policies and prioritized replay (mdp_per_enable) do not combine");
+  if (h->td3) return fail(h, "mdp_approx_enable: inferred policies and MATD3 (mdp_td3_enable) do not combine");
+  if (h->minimax)
+    return fail(h, "mdp_approx_enable: inferred policies and M3DDPG (mdp_minimax_enable) do not combine");
+  if (h->update_mode != 0)
+    return fail(h, "mdp_approx_enable: inferred policies need the strict update mode (throughput mode is not "
+                   "supported)");
+  if (h->comm || h->p2p || h->xbuf || h->cfg.world_size > 1)
+    return fail(h, (std::string("mdp_approx_enable: ") + kApxNoDp).c_str());
+  const Topo& T = h->L.topo;
+  if (T.H != 64 && T.H != 128 && T.H != 256)
+    return fail(h, "mdp_approx_enable: the gradient kernels serve num_units 64, 128 or 256");
+  if (lds_approx_bytes(T) > MDP_LDS_BUDGET)
+    return fail(h, "mdp_approx_enable: the approximator step does not fit the kernels' LDS envelope");
+  const ApxLayout al = apx_layout(h->cfg, h->L);
+  if (!buf_dev) return fail(h, "mdp_approx_enable: buf_dev is null");
+  if (bytes < al.total) return fail(h, "mdp_approx_enable: bytes is smaller than mdp_approx_bytes");
+  MDP_DEV(h, buf_dev, al.total, "mdp_approx_enable", false);
+  char* b = (char*)buf_dev;
+  const int n = h->cfg.n_agents;
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  HIPCHK(h, hipMemsetAsync(b, 0, al.total, h->stream));
+  std::vector<float> beta(4 * (size_t)n * n);
+  for (int q = 0; q < n * n; ++q) {  // as mdp_create: the powers start at beta
+    beta[4 * q] = beta[4 * q + 2] = h->cfg.adam_b1;
+    beta[4 * q + 1] = beta[4 * q + 3] = h->cfg.adam_b2;
+  }
+  HIPCHK(h, hipMemcpyAsync(b + al.beta, beta.data(), 4 * beta.size(), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  h->apx_buf = b;
+  h->apx_region = al.region;
+  h->apx_obs_stride = al.obs_stride;
+  h->apx_slab = (float*)(b + al.slab);
+  h->apx_stat = (double*)(b + al.stat);
+  h->apx_beta = (float*)(b + al.beta);
+  h->apx_ticket = (uint32_t*)(b + al.ticket);
+  h->apx_ctr = (uint32_t*)(b + al.ctr);
+  h->apx_part = (uint64_t*)(b + al.part);
+  h->apx_lambda = lambda;
+  for (int i = 0; i < MDP_MAX_AGENTS; ++i) h->apx_count[i] = 0;
+  h->apx_pending = -1;
+  h->approx = true;
+  h->general_grads = true;  // runs on the general kernels: no actor_pre / critic_pre, no index prefetch
+  drop_graphs(h);
+  return 0;
+}
+
+// the pair (observer, agent) of an approximator entry point `fn` (agent -1: any), or the refusal
+static int need_apx(mdp_handle* h, int32_t observer, int32_t agent, const char* fn) {
+  if (unusable(h)) return -1;
+  const std::string f(fn);
+  if (!h->approx) return fail(h, (f + ": inferred policies are not enabled (mdp_approx_enable)").c_str());
+  const int n = h->cfg.n_agents;
+  if (observer < 0 || observer >= n) return fail(h, (f + ": observer out of range").c_str());
+  if (h->L.topo.ag[observer].local_q)
+    return fail(h, (f + ": observer has a local (DDPG) critic and no approximators").c_str());
+  if (agent == -1) return n > 1 ? 0 : fail(h, (f + ": observer has nobody to approximate").c_str());
+  if (agent < 0 || agent >= n) return fail(h, (f + ": agent out of range").c_str());
+  if (agent == observer) return fail(h, (f + ": agent is the observer itself (no approximator)").c_str());
+  return 0;
+}
+
+int mdp_approx_set_params(mdp_handle* h, int32_t observer, int32_t agent, int32_t which, const float* src, int64_t n) {
+  if (need_apx(h, observer, agent < 0 ? -2 : agent, "mdp_approx_set_params")) return -1;
+  if (which < MDP_APX_NET || which > MDP_APX_GRAD) return fail(h, "mdp_approx_set_params: which must be in 0..4");
+  if (!src) return fail(h, "mdp_approx_set_params: src is null");
+  if (n != net_floats(h, agent, 0)) return fail(h, "mdp_approx_set_params: n differs from the actor's parameter count");
+  h->started = true;
+  const NDesc& d = net_of(h, agent, 0);
+  const std::vector<float> buf = scatter_net(h, agent, 0, src);
+  HIPCHK(h, hipMemcpyAsync(apx_base(h, observer, which) + d.off, buf.data(), 4 * buf.size(), hipMemcpyHostToDevice,
+                           h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  return 0;
+}
+
+int mdp_approx_get_params(mdp_handle* h, int32_t observer, int32_t agent, int32_t which, float* dst, int64_t n) {
+  if (need_apx(h, observer, agent < 0 ? -2 : agent, "mdp_approx_get_params")) return -1;
+  if (which < MDP_APX_NET || which > MDP_APX_GRAD) return fail(h, "mdp_approx_get_params: which must be in 0..4");
+  if (!dst) return fail(h, "mdp_approx_get_params: dst is null");
+  if (n != net_floats(h, agent, 0)) return fail(h, "mdp_approx_get_params: n differs from the actor's parameter count");
+  const NDesc& d = net_of(h, agent, 0);
+  if (which == MDP_APX_GRAD && h->apx_pending == observer) {
+    // a gradient-only launch: its partials are reduced on demand (no optimizer state moves)
+    const int p = agent < observer ? agent : agent - 1;
+    if (apx_reduce(h, observer, agent, p, nullptr)) return -1;
+  }
+  std::vector<float> buf(d.size);
+  HIPCHK(h, hipMemcpyAsync(buf.data(), apx_base(h, observer, which) + d.off, 4 * buf.size(), hipMemcpyDeviceToHost,
+                           h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  int64_t s = 0;
+  for (int t = 0; t < 6; ++t) {
+    int rows, cols;
+    logical_shape(h, agent, 0, t, &rows, &cols);
+    for (int r = 0; r < rows; ++r, s += cols)
+      std::memcpy(dst + s, buf.data() + (d.t[t].off - d.off) + (int64_t)r * d.t[t].cols, 4 * (int64_t)cols);
+  }
+  return 0;
+}
+
+int mdp_approx_get_beta_powers(mdp_handle* h, int32_t observer, int32_t agent, float out2[2]) {
+  if (need_apx(h, observer, agent < 0 ? -2 : agent, "mdp_approx_get_beta_powers")) return -1;
+  if (!out2) return fail(h, "mdp_approx_get_beta_powers: out2 is null");
+  const float* src = h->apx_beta + ((int64_t)observer * h->cfg.n_agents + agent) * 4;
+  HIPCHK(h, hipMemcpyAsync(out2, src, 8, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  return 0;
+}
+
+int mdp_approx_set_beta_powers(mdp_handle* h, int32_t observer, int32_t agent, const float in2[2]) {
+  if (need_apx(h, observer, agent < 0 ? -2 : agent, "mdp_approx_set_beta_powers")) return -1;
+  if (!in2) return fail(h, "mdp_approx_set_beta_powers: in2 is null");
+  float* dst = h->apx_beta + ((int64_t)observer * h->cfg.n_agents + agent) * 4;
+  HIPCHK(h, hipMemcpyAsync(dst, in2, 8, hipMemcpyHostToDevice, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  return 0;
+}
+
+int mdp_approx_info(mdp_handle* h, int32_t observer, int32_t agent, double out4[4]) {
+  if (need_apx(h, observer, agent < 0 ? -2 : agent, "mdp_approx_info")) return -1;
+  if (!out4) return fail(h, "mdp_approx_info: out4 is null");
+  const int64_t nwg = h->L.nwg;
+  std::vector<double> st(8 * (size_t)nwg);
+  const double* src = h->apx_stat + ((int64_t)observer * h->cfg.n_agents + agent) * nwg * 8;
+  HIPCHK(h, hipMemcpyAsync(st.data(), src, 8 * st.size(), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  double ce = 0.0, en = 0.0;
+  for (int64_t w = 0; w < nwg; ++w) {
+    ce += st[8 * w];
+    en += st[8 * w + 1];
+  }
+  out4[0] = ce / h->cfg.batch_size;
+  out4[1] = en / h->cfg.batch_size;
+  out4[2] = out4[0] - (double)h->apx_lambda * out4[1];
+  out4[3] = (double)h->apx_count[observer];
+  return 0;
+}
+
+int mdp_approx_logits(mdp_handle* h, int32_t observer, int32_t agent, int32_t target, const float* obs_dev,
+                      float* logits_dev, int32_t rows) {
+  if (need_apx(h, observer, agent < 0 ? -2 : agent, "mdp_approx_logits")) return -1;
+  if (rows <= 0) return 0;
+  const ADesc& ag = h->L.topo.ag[agent];
+  h->started = true;
+  MDP_DEV(h, obs_dev, 4 * (int64_t)rows * ag.obs_dim, "mdp_approx_logits", false);
+  MDP_DEV(h, logits_dev, 4 * (int64_t)rows * MDP_ACT_DIM, "mdp_approx_logits", false);
+  EvalArgs a;
+  a.P = apx_base(h, observer, target ? MDP_APX_TARGET : MDP_APX_NET);
+  a.net = ag.actor;
+  a.in = ag.obs_dim;
+  a.rows = rows;
+  a.x = obs_dev;
+  a.out = logits_dev;
+  a.gumbel = 0;
+  a.act_w = MDP_ACT_DIM;
+  a.u = nullptr;
+  a.seed = h->cfg.seed;
+  a.stream = 0;
+  a.ctr = 0;
+  HIPCHK(h, mdp_launch_eval(a, h->L.topo.H, lds_eval_bytes(a.in, h->L.topo.H), h->stream));
+  return 0;
+}
+
+static int apx_rows(mdp_handle* h, int32_t observer, const int32_t* idx_dev, const char* fn) {
+  if (need_apx(h, observer, -1, fn)) return -1;
+  if (h->len <= 0) return fail(h, (std::string(fn) + ": the replay buffer is empty").c_str());
+  return need_dev(h, idx_dev, 4 * (int64_t)h->cfg.batch_size, fn, "idx_dev", false);
+}
+
+int mdp_approx_grad(mdp_handle* h, int32_t observer, const int32_t* idx_dev) {
+  if (apx_rows(h, observer, idx_dev, "mdp_approx_grad")) return -1;
+  h->trained = true;
+  const int rc = do_approx_grad(h, observer, idx_dev);
+  if (!rc) h->apx_pending = observer;
+  return rc;
+}
+
+int mdp_approx_step(mdp_handle* h, int32_t observer, const int32_t* idx_dev) {
+  if (apx_rows(h, observer, idx_dev, "mdp_approx_step")) return -1;
+  h->trained = true;
+  const int rc = do_approx_step(h, observer, idx_dev);
+  if (!rc) {
+    h->apx_count[observer] += 1;
+    h->apx_pending = -1;
+  }
+  return rc;
 }
 
 static int need_per(mdp_handle* h, int32_t agent, const char* fn) {

@@ -29,6 +29,11 @@
 //   || wave 0: head, fp64 TD ... as the uniform kernel
 // k_actor_grad<.., MM>: after the critic's L2 the same three steps on the critic, a^ into
 //   the critic input, the critic's L1 and L2 again, then the uniform kernel's backward
+// k_critic_grad<.., APX> (inferred policies): the uniform kernel with the
+//   target actors j != agent read from the agent's target approximators
+// k_approx_grad: per (approximated agent, row tile)
+//   gather obs_j, act_j | L1 || L2 || head, log-softmax, loss terms, seed (wave 0)
+//   || dW3, db3, d2 || dh1 tiles + dW2 tiles || dW1, db1
 // k_actor_grad (maddpg.py:37-58):
 //   gather | actor L1 || L2 || head, Gumbel a_i, critic input || critic L1 || L2
 //   || head q, d2 || dh1c tiles || da, softmax backward + reg (wave 0)
@@ -455,9 +460,13 @@ __device__ __forceinline__ void critic_backward(const float* th, const NDesc& nd
 // MM (A = CriticArgsMm): the M3DDPG step -- after the target critic's forward its
 // backward to the other agents' target actions, those moved against Q', and the
 // target critic again on the moved input; strict mode, MADDPG critics
-template <int H, bool PER = false, class A = CriticArgs, bool TWIN = false, bool MM = false>
+// APX (A = CriticArgsApx): inferred policies -- the target action of every agent
+// j != agent comes from this agent's target approximator of j (a.apx_target,
+// agent j's actor span) instead of target actor j; MADDPG critics
+template <int H, bool PER = false, class A = CriticArgs, bool TWIN = false, bool MM = false, bool APX = false>
 __device__ __forceinline__ void critic_body(const A& a, const Topo& T, const int blk) {
   static_assert(!(MM && (TWIN || PER)), "minimax combines with neither twin critics nor prioritized replay");
+  static_assert(!(APX && (MM || TWIN || PER)), "inferred policies combine with none of the other options");
   // (no MDP_KARG_TOUCH here: at H = 128 it turned the kernel's 47 spilled
   // SGPRs into 91 spilled VGPRs)
   constexpr int NT = H / 16;
@@ -581,6 +590,9 @@ __device__ __forceinline__ void critic_body(const A& a, const Topo& T, const int
         const ADesc& aj = T.ag[lq ? a.agent : g0 + jb];
         const NDesc& net = actor ? aj.actor : nd;
         const float* P = actor ? a.target : a.theta;
+        if constexpr (APX) {
+          if (actor && g0 + jb != a.agent) P = a.apx_target;
+        }
         const int slot = (actor ? jb : G) * S;
         TileJob j;
         j.k0 = 0;
@@ -640,7 +652,11 @@ __device__ __forceinline__ void critic_body(const A& a, const Topo& T, const int
     for (int jb = wave; jb < nj; jb += nw) {
       if (jb < ng) {
         const NDesc& an = T.ag[lq ? a.agent : g0 + jb].actor;
-        head_mfma<H / 4>(hB + jb * S, ldh, H, a.target + an.t[4].off, a.target + an.t[5].off, MDP_ACT_DIM,
+        const float* PA = a.target;
+        if constexpr (APX) {
+          if (g0 + jb != a.agent) PA = a.apx_target;
+        }
+        head_mfma<H / 4>(hB + jb * S, ldh, H, PA + an.t[4].off, PA + an.t[5].off, MDP_ACT_DIM,
                          lg + jb * MDP_R * 8, 8);
       } else {
         head_mfma<H / 4>(h2c, ldh, H, a.theta + nd.t[4].off, a.theta + nd.t[5].off, 1, qv, 8);
@@ -843,9 +859,10 @@ __device__ __forceinline__ void critic_body(const A& a, const Topo& T, const int
 // PER: the prioritized-replay twin (A = CriticArgsPer), strict mode only
 // TWIN: the MATD3 twin (A = CriticArgsTwin), strict mode only
 // MM: the M3DDPG twin (A = CriticArgsMm), strict mode only
-template <int H, bool PER = false, class A = CriticArgs, bool TWIN = false, bool MM = false>
+// APX: the inferred-policies twin (A = CriticArgsApx), strict mode only
+template <int H, bool PER = false, class A = CriticArgs, bool TWIN = false, bool MM = false, bool APX = false>
 __global__ __launch_bounds__(MDP_GEN_THREADS) void k_critic_grad(A a) {
-  critic_body<H, PER, A, TWIN, MM>(a, a.topo, blockIdx.x);
+  critic_body<H, PER, A, TWIN, MM, APX>(a, a.topo, blockIdx.x);
 }
 
 // AA: ActorArgs, or the Topo-less ActorArgsHead of a gradient-pair launch
@@ -1177,6 +1194,129 @@ __global__ __launch_bounds__(MDP_GEN_THREADS) void k_actor_grad(AA a) {
   actor_body<H, AA, MM>(a, a.topo, blockIdx.x);
 }
 
+// Inferred policies: one gradient step's raw gradients of the
+// approximators phi_i^j of observer i, one workgroup per (pair, 16-row tile):
+//   gather obs_j, act_j | L1 || L2 || wave 0: head, log-softmax, loss terms, seed
+//   || dW3, db3, d2 || dh1 tiles + dW2 tiles || dW1, db1
+// -- k_actor_grad without its critic half.  loss = mean_b[-sum_c a_c log p_c -
+// lambda H(p)] over the first A_j logits, a = the replayed action; log p is the
+// log-softmax, never the log of a probability.  4 H threads: one forward tile
+// per wave (NT waves), the backward's NT + NT^2 tiles dealt over them.
+template <int H>
+__global__ __launch_bounds__(4 * H) void k_approx_grad(ApproxArgs a) {
+#pragma clang fp contract(off)
+  constexpr int NT = H / 16;
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  const Topo& T = a.topo;
+  const int pair = (int)blockIdx.x / a.nwg, blk = (int)blockIdx.x - pair * a.nwg;
+  const int j = a.agents[pair];
+  const ADesc& aj = T.ag[j];
+  const NDesc& na = aj.actor;
+  const int od = aj.obs_dim, ldo = lds_ld(od), ldh = H + 1, S = MDP_R * ldh;
+  LdsCarve cv(lds);
+  float* xo = cv.take(MDP_R * ldo);
+  float* h1 = cv.take(S);
+  float* h2 = cv.take(S);
+  float* d2 = cv.take(S);
+  float* d1 = cv.take(S);
+  float* lg = cv.take(MDP_R * 8);
+  float* av = cv.take(MDP_R * 8);
+  float* dl = cv.take(MDP_R * 8);
+  const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63, nw = blockDim.x >> 6;
+  const int r0 = blk * MDP_R;
+  const int nvalid = min(MDP_R, a.B - r0);
+  const float* P = a.phi;
+  float pf[MDP_KC];
+  f32x4 pft[4];
+  pf_load(pf, P + na.t[0].off, H, wave, 0, od);
+  // only obs_j and act_j of the rows (rows past the batch: zeros)
+  for (int e = tid; e < MDP_R * (od + 8); e += blockDim.x) {
+    const int r = e / (od + 8), c = e - r * (od + 8);
+    const float* row = a.replay + (int64_t)a.idx[r0 + min(r, nvalid - 1)] * T.row_stride;
+    if (c < od) xo[r * ldo + c] = r < nvalid ? row[aj.obs_off + c] : 0.f;
+    else if (c - od < MDP_ACT_DIM) av[r * 8 + c - od] = r < nvalid ? row[aj.act_off + c - od] : 0.f;
+  }
+  __syncthreads();
+  fwd_tile_pf<true>(xo, ldo, 0, od, P + na.t[0].off, P + na.t[1].off, H, nullptr, 0, h1, ldh, wave, pf);
+  pf_load(pf, P + na.t[2].off, H, wave, 0, H);
+  __syncthreads();
+  fwd_tile_pf<true>(h1, ldh, 0, H, P + na.t[2].off, P + na.t[3].off, H, nullptr, 0, h2, ldh, wave, pf);
+  pf_load_t(pft, P + na.t[2].off, H, wave);  // dh1 = d2 W2^T
+  __syncthreads();
+  if (wave == 0) {
+    head_mfma<H / 4>(h2, ldh, H, P + na.t[4].off, P + na.t[5].off, MDP_ACT_DIM, lg, 8);
+    wave_sync();
+    double s_ce = 0.0, s_en = 0.0;
+    if (lane < MDP_R) {
+      const int A = topo_act_w(T, j);
+      const float* l = lg + lane * 8;
+      const float* ac = av + lane * 8;
+      float mx = l[0];
+      for (int k = 1; k < MDP_ACT_DIM; ++k)
+        if (k < A) mx = fmaxf(mx, l[k]);
+      float ex[MDP_ACT_DIM], lp[MDP_ACT_DIM], se = 0.f, sa = 0.f;
+      for (int k = 0; k < MDP_ACT_DIM; ++k) {
+        ex[k] = k < A ? expf(l[k] - mx) : 0.f;
+        se = se + ex[k];
+        sa = sa + (k < A ? ac[k] : 0.f);
+      }
+      const float ls = logf(se);
+      float ce = 0.f, en = 0.f;
+      for (int k = 0; k < MDP_ACT_DIM; ++k) {
+        lp[k] = k < A ? (l[k] - mx) - ls : 0.f;
+        ex[k] = ex[k] / se;
+        ce = ce - (k < A ? ac[k] * lp[k] : 0.f);
+        en = en - ex[k] * lp[k];
+      }
+      for (int k = 0; k < MDP_ACT_DIM; ++k) {
+        const float g = ((ex[k] * sa - ac[k]) + a.lambda * (ex[k] * (lp[k] + en))) * a.inv_b;
+        dl[lane * 8 + k] = (lane < nvalid && k < A) ? g : 0.f;
+      }
+      if (lane < nvalid) {
+        s_ce = (double)ce;
+        s_en = (double)en;
+      }
+    }
+    s_ce = sum16(s_ce);
+    s_en = sum16(s_en);
+    if (lane == 0) {
+      double* st = a.slab_stat + ((int64_t)j * a.nwg + blk) * 8;
+      st[0] = s_ce;
+      st[1] = s_en;
+    }
+  }
+  __syncthreads();
+  // backward: dW3, db3, d2 = (dl @ W3^T) masked by h2 > 0
+  float* slab = a.slab + ((int64_t)pair * a.nwg + blk) * a.slab_stride - na.off;
+  const float* W3 = P + na.t[4].off;
+  for (int e = tid; e < H * MDP_ACT_DIM; e += blockDim.x) {
+    const int h = e / MDP_ACT_DIM, k = e - h * MDP_ACT_DIM;
+    float s = 0.f;
+    for (int r = 0; r < MDP_R; ++r) s = fmaf(h2[r * ldh + h], dl[r * 8 + k], s);
+    slab[na.t[4].off + e] = s;
+  }
+  if (tid < MDP_ACT_DIM) {
+    float s = 0.f;
+    for (int r = 0; r < MDP_R; ++r) s += dl[r * 8 + tid];
+    slab[na.t[5].off + tid] = s;
+  }
+  for (int e = tid; e < MDP_R * H; e += blockDim.x) {
+    const int r = e / H, h = e - r * H;
+    float s = 0.f;
+    for (int k = 0; k < MDP_ACT_DIM; ++k) s = fmaf(dl[r * 8 + k], W3[h * MDP_ACT_DIM + k], s);
+    d2[r * ldh + h] = h2[r * ldh + h] > 0.f ? s : 0.f;
+  }
+  __syncthreads();
+  for (int t = wave; t < NT + NT * NT; t += nw) {
+    if (t < NT) dgrad_tile_relu_pf(d2, ldh, H, P + na.t[2].off, h1, ldh, d1, ldh, t, pft);
+    else wgrad_tile(h1, ldh, H, d2, ldh, H, slab + na.t[2].off, t - NT);
+  }
+  colsum16(d2, ldh, H, slab + na.t[3].off);
+  __syncthreads();
+  wgrad_waves(xo, ldo, od, d1, ldh, H, slab + na.t[0].off, 0, nw);
+  colsum16(d1, ldh, H, slab + na.t[1].off);
+}
+
 // throughput mode: agent i's critic step (workgroups [0, B/16)) and actor step
 // (the rest) in one launch -- no kernel boundary between them, and the actor
 // step's workgroups start on the CUs the critic step's finished ones free
@@ -1252,6 +1392,31 @@ hipError_t launch_actor_mm(const ActorArgsMm& a, int lds, hipStream_t s) {
   return hipGetLastError();
 }
 template <int H>
+hipError_t launch_critic_apx(const CriticArgsApx& a, int lds, hipStream_t s) {
+  static bool attr = false;
+  if (!attr) {
+    (void)hipFuncSetAttribute((const void*)k_critic_grad<H, false, CriticArgsApx, false, false, true>,
+                              hipFuncAttributeMaxDynamicSharedMemorySize, MDP_LDS_BUDGET);
+    (void)hipGetLastError();
+    attr = true;
+  }
+  mdp_launch(k_critic_grad<H, false, CriticArgsApx, false, false, true>, dim3((a.B + MDP_R - 1) / MDP_R),
+             dim3(MDP_GEN_THREADS), lds, s, a);
+  return hipGetLastError();
+}
+template <int H>
+hipError_t launch_approx(const ApproxArgs& a, int lds, hipStream_t s) {
+  static bool attr = false;
+  if (!attr) {
+    (void)hipFuncSetAttribute((const void*)k_approx_grad<H>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                              MDP_LDS_BUDGET);
+    (void)hipGetLastError();
+    attr = true;
+  }
+  mdp_launch(k_approx_grad<H>, dim3(a.m * a.nwg), dim3(4 * H), lds, s, a);
+  return hipGetLastError();
+}
+template <int H>
 hipError_t launch_actor(const ActorArgs& a, int lds, hipStream_t s) {
   static bool attr = false;
   if (!attr) {
@@ -1324,6 +1489,22 @@ hipError_t mdp_launch_actor_grad_mm(const ActorArgsMm& a, int H, int lds_bytes, 
     case 64: return launch_actor_mm<64>(a, lds_bytes, s);
     case 128: return launch_actor_mm<128>(a, lds_bytes, s);
     case 256: return launch_actor_mm<256>(a, lds_bytes, s);
+    default: return hipErrorInvalidValue;
+  }
+}
+hipError_t mdp_launch_critic_grad_apx(const CriticArgsApx& a, int H, int lds_bytes, hipStream_t s) {
+  switch (H) {
+    case 64: return launch_critic_apx<64>(a, lds_bytes, s);
+    case 128: return launch_critic_apx<128>(a, lds_bytes, s);
+    case 256: return launch_critic_apx<256>(a, lds_bytes, s);
+    default: return hipErrorInvalidValue;
+  }
+}
+hipError_t mdp_launch_approx_grad(const ApproxArgs& a, int H, int lds_bytes, hipStream_t s) {
+  switch (H) {
+    case 64: return launch_approx<64>(a, lds_bytes, s);
+    case 128: return launch_approx<128>(a, lds_bytes, s);
+    case 256: return launch_approx<256>(a, lds_bytes, s);
     default: return hipErrorInvalidValue;
   }
 }

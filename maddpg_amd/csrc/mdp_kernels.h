@@ -89,6 +89,33 @@ struct CriticArgsMm : CriticArgs {
   float* adv_out;
 };
 
+// Inferred policies (strict mode, general kernels): the argument block
+// of the critic kernel's approximator instantiation.  apx_target is the
+// param-space base of the observing agent's target approximators (each in the
+// approximated agent's actor span, the arena's NDesc offsets): the target
+// action of every agent j != agent comes from it instead of `target`
+struct CriticArgsApx : CriticArgs {
+  const float* apx_target;
+};
+
+// k_approx_grad: one workgroup per (pair, 16-row tile), pair p = workgroup / nwg
+// approximates agent agents[p] for one observing agent.  phi: param-space base
+// of the observer's approximators; slab [m][nwg][slab_stride] partial gradients
+// (net-relative); slab_stat [n][nwg][8] of this observer, indexed by the
+// approximated agent: {sum of cross-entropies, sum of entropies} of the tile
+struct ApproxArgs {
+  int B, m, nwg;
+  int agents[MDP_MAX_AGENTS];
+  const float* phi;
+  const float* replay;
+  const int32_t* idx;
+  float inv_b, lambda;
+  float* slab;
+  int slab_stride;
+  double* slab_stat;
+  Topo topo;
+};
+
 // precomputed critic-step work of one batch row (k_actor_grad_r's extra
 // workgroups -> k_critic_grad_r in critic_post mode):
 //   h1 [64] | h2 [64] (critic forward) | target-critic L1 accumulator [64] | q | pad 3 | a~ [16]
@@ -436,6 +463,14 @@ inline int lds_actor_bytes(const Topo& t) {
 inline int lds_mm_dxa(const Topo& t) { return mdp_r4(16 * MDP_ACT_DIM * t.n); }
 inline int lds_critic_mm_bytes(const Topo& t, int G) { return lds_critic_bytes(t, G) + 4 * lds_mm_dxa(t); }
 inline int lds_actor_mm_bytes(const Topo& t) { return lds_actor_bytes(t) + 4 * lds_mm_dxa(t); }
+// k_approx_grad: the rows' obs_j and act_j, four activation slots, logits and their seed
+inline int mdp_approx_threads(int H) { return 4 * H; }  // one forward tile per wave
+inline int lds_approx_bytes(const Topo& t) {
+  int omax = 1;
+  for (int j = 0; j < t.n; ++j) omax = t.ag[j].obs_dim > omax ? t.ag[j].obs_dim : omax;
+  const int R = 16, S = R * (t.H + 1);
+  return 4 * (mdp_r4(R * mdp_ld(omax)) + 4 * mdp_r4(S) + 3 * mdp_r4(R * 8));
+}
 #define MDP_LDS_BUDGET (160 * 1024)
 // fast (register-resident, H = 64) variants in mdp_grads_r.hip
 inline int lds_critic_r_bytes(const Topo& t, int agent) {
@@ -519,6 +554,8 @@ hipError_t mdp_launch_critic_grad_per(const CriticArgsPer& a, int H, int lds_byt
 hipError_t mdp_launch_critic_grad_twin(const CriticArgsTwin& a, int H, int lds_bytes, hipStream_t s);
 hipError_t mdp_launch_critic_grad_mm(const CriticArgsMm& a, int H, int lds_bytes, hipStream_t s);
 hipError_t mdp_launch_actor_grad_mm(const ActorArgsMm& a, int H, int lds_bytes, hipStream_t s);
+hipError_t mdp_launch_critic_grad_apx(const CriticArgsApx& a, int H, int lds_bytes, hipStream_t s);
+hipError_t mdp_launch_approx_grad(const ApproxArgs& a, int H, int lds_bytes, hipStream_t s);
 hipError_t mdp_launch_critic_grad_r_per(const CriticArgsPer& a, int lds_bytes, hipStream_t s);
 hipError_t mdp_launch_actor_grad_r(const ActorArgs& a, int lds_bytes, hipStream_t s);
 hipError_t mdp_launch_rollout(const RolloutArgs& a, int H, int lds_bytes, hipStream_t s);

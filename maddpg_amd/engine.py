@@ -63,8 +63,14 @@ class Engine:
                  adam_eps=1e-8, seed=0, world_size=1, rank=0, device=None, episode_log_rows=0,
                  prioritized=False, per_alpha=0.6, per_beta0=0.4, per_beta_inc=0.001, per_eps=0.01,
                  per_abs_err_upper=1.0, act_dims=None, td3=False, policy_delay=2, minimax=False, adv_eps=1e-3,
-                 adv_eps_s=1e-5, minimax_eps=None):
-        """minimax: M3DDPG (mdp_minimax_enable) -- in the critic target and the actor
+                 adv_eps_s=1e-5, minimax_eps=None, approx=False, approx_lambda=1e-3):
+        """approx: MADDPG with inferred policies (mdp_approx_enable; Lowe et al. 2017,
+        section 4.2) -- every agent i with a MADDPG critic learns an approximator of
+        every other agent's policy from replay (cross-entropy of the replayed
+        action + approx_lambda x entropy) and builds its TD target from the
+        approximators' target networks instead of the others' target actors;
+        strict mode, one GPU, none of prioritized / td3 / minimax.
+        minimax: M3DDPG (mdp_minimax_enable) -- in the critic target and the actor
         loss the other agents' actions move one normalised gradient step against
         this agent's Q; rates adv_eps across the sides of num_adversaries and
         adv_eps_s within a side, or minimax_eps, an n x n array eps[i][j] (which
@@ -92,6 +98,16 @@ class Engine:
         self.num_envs = int(num_envs)
         self.scenario = scenario
         self.world_size, self.rank = int(world_size), int(rank)
+        self.approx = bool(approx)
+        self.approx_lambda = float(approx_lambda)
+        self.approx_buf = None
+        if self.approx:     # refused here, before anything is allocated or created on the device
+            other = [k for k, on in (("prioritized", prioritized), ("td3", td3),
+                                     ("minimax", minimax or minimax_eps is not None),
+                                     ("world_size > 1", self.world_size > 1)) if on]
+            if other or not (np.isfinite(self.approx_lambda) and self.approx_lambda >= 0):
+                raise _lib.MdpError(f"approx does not combine with {', '.join(other)} (mdp_approx_enable)" if other
+                                    else f"approx_lambda must be finite and >= 0, got {approx_lambda!r}")
         cfg = MdpConfig()
         cfg.n_agents = n
         for i in range(n):
@@ -182,6 +198,8 @@ class Engine:
             from .envs import minimax_eps as _eps
             self._minimax_enable(_eps(n, int(num_adversaries), adv_eps, adv_eps_s) if minimax_eps is None
                                  else minimax_eps)
+        if self.approx:
+            self._approx_enable(self.approx_lambda)
 
     # ------------------------------------------------------------ plumbing
     def _c(self, name, *args):
@@ -334,7 +352,7 @@ class Engine:
         rng = np.random.default_rng(seed)
         H = self.num_units
 
-        def draw(i, which):
+        def draw(i, which, write=True):
             shapes = self._flat_shapes(i, which)
             p = {}
             for k, (r, c) in zip(TENSOR_NAMES, shapes):
@@ -343,7 +361,9 @@ class Engine:
                     p[k] = rng.uniform(-lim, lim, size=(r, c)).astype(np.float32)
                 else:
                     p[k] = np.zeros((r, c), np.float32)
-            self.set_params(i, which, p)
+            if write:
+                self.set_params(i, which, p)
+            return p
 
         for i in range(self.n):
             for which in ("actor", "critic", "tgt_actor", "tgt_critic"):
@@ -352,6 +372,12 @@ class Engine:
             for i in range(self.n):
                 for which in ("critic2", "tgt_critic2"):
                     draw(i, which)
+        # the approximators after all of those (a seed's existing nets do not
+        # move); each target starts as a copy of its approximator
+        for i, j in self.approx_pairs():
+            p = draw(j, "actor", write=False)
+            self.set_approx_params(i, j, "net", p)
+            self.set_approx_params(i, j, "tgt", p)
         return H
 
     # --------------------------------------------------------- checkpoint
@@ -372,6 +398,11 @@ class Engine:
             out[f"agent_{i}/critic/beta_power"] = self.get_beta_powers(i, 1)
             if self.td3:
                 out[f"agent_{i}/critic2/beta_power"] = self.get_beta_powers(i, 2)
+        for i, j in self.approx_pairs():
+            for w in self.APPROX_SETS:
+                for k, v in self.get_approx_params(i, j, w).items():
+                    out[f"agent_{i}/approx_{j}/{w}/{k}"] = v
+            out[f"agent_{i}/approx_{j}/beta_power"] = self.get_approx_beta_powers(i, j)
         return out
 
     def load_state_dict(self, sd, agents=None):
@@ -390,6 +421,13 @@ class Engine:
                 for w in self.TD3_SETS:
                     self.set_params(i, w, {k: sd[f"agent_{i}/{w}/{k}"] for k in TENSOR_NAMES})
                 self.set_beta_powers(i, 2, sd[f"agent_{i}/critic2/beta_power"])
+            # the approximators: restored when the engine has them and the checkpoint
+            # holds them (a MADDPG checkpoint leaves them as they are)
+            for oi, j in self.approx_pairs():
+                if oi == i and f"agent_{i}/approx_{j}/beta_power" in sd:
+                    for w in self.APPROX_SETS:
+                        self.set_approx_params(i, j, w, {k: sd[f"agent_{i}/approx_{j}/{w}/{k}"] for k in TENSOR_NAMES})
+                    self.set_approx_beta_powers(i, j, sd[f"agent_{i}/approx_{j}/beta_power"])
 
     @staticmethod
     def checkpoint_path(fname):
@@ -407,6 +445,9 @@ class Engine:
         file; no .meta -- the graph is built by code on both sides)."""
         if fmt == "tf1" and self.td3:
             raise ValueError("save_state(fmt='tf1') on a TD3 engine: the second critic has no reference variable "
+                             "names; save as npz")
+        if fmt == "tf1" and self.approx:
+            raise ValueError("save_state(fmt='tf1') on an approx engine: the approximators have no reference variable "
                              "names; save as npz")
         if fmt == "tf1":
             from .common import tf_checkpoint as tfc
@@ -568,6 +609,137 @@ class Engine:
         self._c("mdp_minimax_debug_adv", *[None if b is None else self._ptr(b) for b in bufs])
         self._adv_bufs = bufs   # keep them alive while the handle points at them
         return tuple(bufs)
+
+    # ------------------------------------------------- inferred policies
+    APPROX_SETS = ("net", "tgt", "m", "v")
+
+    def _approx_enable(self, lam):
+        """approximators of the other agents' policies (mdp_approx_enable): their
+        nets, targets, Adam slots, partials and sync area live in a second device
+        buffer owned here"""
+        nbytes = self.lib.mdp_approx_bytes(ctypes.byref(self.cfg))
+        if nbytes < 0:
+            raise ValueError("mdp_approx_bytes refused the configuration")
+        with torch.cuda.device(self.device):
+            self.approx_buf = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        try:
+            self._c("mdp_approx_enable", self._ptr(self.approx_buf), nbytes, float(lam))
+        except Exception:
+            self.approx_buf = None
+            self.close()
+            raise
+
+    def approx_pairs(self):
+        """(observer, agent) of every approximator: observers with a MADDPG critic"""
+        if not getattr(self, "approx", False):
+            return []
+        return [(i, j) for i in range(self.n) if not self.local_q[i] for j in range(self.n) if j != i]
+
+    def set_approx_params(self, observer, agent, which, params):
+        """set `which` (net, tgt, m, v, grad) of observer's approximator of agent, in
+        agent's actor layout (mdp_approx_set_params)"""
+        flat = self._flat_params(agent, "actor", params)
+        self._c("mdp_approx_set_params", observer, agent, _lib.APX_WHICH[which], _lib.fptr(flat), flat.size)
+
+    def get_approx_params(self, observer, agent, which):
+        shapes = self._flat_shapes(agent, "actor")
+        n = sum(r * c for r, c in shapes)
+        flat = np.empty(n, np.float32)
+        self._c("mdp_approx_get_params", observer, agent, _lib.APX_WHICH[which], _lib.fptr(flat), n)
+        out, s = {}, 0
+        for k, (r, c) in zip(TENSOR_NAMES, shapes):
+            a = flat[s:s + r * c].reshape(r, c)
+            out[k] = a[0].copy() if k.startswith("b") else a.copy()
+            s += r * c
+        return out
+
+    def get_approx_beta_powers(self, observer, agent):
+        b = np.empty(2, np.float32)
+        self._c("mdp_approx_get_beta_powers", observer, agent, _lib.fptr(b))
+        return b
+
+    def set_approx_beta_powers(self, observer, agent, b):
+        b = np.ascontiguousarray(b, np.float32)
+        self._c("mdp_approx_set_beta_powers", observer, agent, _lib.fptr(b))
+
+    def approx_info(self, observer, agent):
+        """{cross_entropy, entropy, loss, updates} of the pair's last gradient launch (mdp_approx_info)"""
+        out = (ctypes.c_double * 4)()
+        self._c("mdp_approx_info", int(observer), int(agent), out)
+        return {"cross_entropy": out[0], "entropy": out[1], "loss": out[2], "updates": int(out[3])}
+
+    def approx_logits(self, observer, agent, obs, target=False):
+        """actor_logits on observer's approximator of agent (mdp_approx_logits)"""
+        obs = obs.to(self.device, torch.float32).contiguous()
+        out = torch.empty((obs.shape[0], _lib.ACT_DIM), dtype=torch.float32, device=self.device)
+        self.sync_in()
+        self._c("mdp_approx_logits", observer, agent, 1 if target else 0, self._ptr(obs), self._ptr(out), obs.shape[0])
+        self.sync_out()
+        return self._narrow(agent, out)
+
+    def _approx_rows(self, name, observer, idx):
+        if idx is None:
+            raise ValueError(f"{name}: idx (the batch_size replay rows) is required")
+        self._sized("idx", idx, self.batch_size)
+        idx = idx.to(self.device, torch.int32).contiguous()
+        self.sync_in()
+        self._c(name, observer, self._ptr(idx))
+        self._keep = [idx]
+        self.sync_out()
+
+    def approx_grad(self, observer, idx):
+        """only the gradient kernel of observer's approximators on rows idx [batch_size]
+        (mdp_approx_grad); get_approx_params(.., 'grad') then reads the raw gradients"""
+        self._approx_rows("mdp_approx_grad", observer, idx)
+
+    def approx_step(self, observer, idx):
+        """one gradient step of every approximator of observer on rows idx (mdp_approx_step)"""
+        self._approx_rows("mdp_approx_step", observer, idx)
+
+    def approx_kl(self, observer, agent, obs):
+        """mean KL(softmax(actor_agent) || softmax(approximator)) over the rows of obs"""
+        lp = torch.log_softmax(self.actor_logits(agent, obs).double(), -1)
+        lq = torch.log_softmax(self.approx_logits(observer, agent, obs).double(), -1)
+        return float((lp.exp() * (lp - lq)).sum(-1).mean())
+
+    def approx_quality(self, idx=None):
+        """How well the approximators fit on replay rows idx (None: a fresh draw of
+        batch_size rows that leaves the training index stream where it was).  Per
+        pair (observer, agent): the mean cross-entropy of the replayed actions
+        under the approximator ("ce"), under the agent's own policy ("ce_true") and
+        the mean KL(policy || approximator) ("kl"); plus the means over all pairs."""
+        if idx is None:
+            st = self.get_rng_state()
+            idx = self.make_index(self.batch_size)
+            self.set_rng_state(st)
+        rows = self.sample_rows(idx.to(self.device, torch.int32))
+        self.sync_out()
+        A = _lib.ACT_DIM
+        pairs = {}
+        for i, j in self.approx_pairs():
+            lay, w = self.row_layout[j], self.act_dims[j]
+            obs = rows[:, lay[0]:lay[0] + self.obs_dims[j]].contiguous()
+            act = rows[:, lay[1]:lay[1] + A][:, :w].double()
+            lq = torch.log_softmax(self.approx_logits(i, j, obs).double(), -1)
+            lp = torch.log_softmax(self.actor_logits(j, obs).double(), -1)
+            pairs[(i, j)] = dict(ce=float(-(act * lq).sum(-1).mean()), ce_true=float(-(act * lp).sum(-1).mean()),
+                                 kl=float((lp.exp() * (lp - lq)).sum(-1).mean()))
+        out = dict(pairs=pairs)
+        for k in ("ce", "ce_true", "kl"):
+            out["mean_" + k] = float(np.mean([v[k] for v in pairs.values()])) if pairs else float("nan")
+        return out
+
+    APPROX_REGIONS = ("net", "target", "adam_m", "adam_v", "grad")
+
+    def approx_region(self, observer, name):
+        """float32 view of one of observer's five param-space regions in the
+        approximator buffer (APPROX_REGIONS), laid out as the arena's regions:
+        its approximator of agent j lies in agent j's actor span"""
+        if not self.approx:
+            raise _lib.MdpError("approx_region: inferred policies are not enabled")
+        stride = (4 * self.param_floats + 255) // 256 * 256
+        k = 5 * observer + self.APPROX_REGIONS.index(name)
+        return self.approx_buf[k * stride: k * stride + 4 * self.param_floats].view(torch.float32)
 
     TD3_REGIONS = ("theta2", "target2", "adam_m2", "adam_v2", "grad2")
 

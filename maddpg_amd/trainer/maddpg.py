@@ -25,6 +25,11 @@ With ``args.minimax`` (``--minimax``, ``args.adv_eps`` / ``args.adv_eps_s`` defa
 M3DDPG one (``DESIGN.md`` section 20): ``p_loss`` and ``mean(target_q_next)`` are
 taken at the perturbed actions.
 
+With ``args.approx_policies`` (``--approx-policies``, ``args.approx_lambda`` default
+1e-3) the session's engine learns approximators of the other agents' policies
+from replay and builds every TD target from them (``DESIGN.md`` section 21); the
+returned list is unchanged.
+
 ``model`` must be the reference's ``mlp_model`` (``train.py:39-46``: two
 hidden ReLU layers of ``args.num_units`` and a linear output, TF
 ``fully_connected`` with Xavier-uniform weights) -- the architecture the HIP

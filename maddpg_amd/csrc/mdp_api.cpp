@@ -15,7 +15,6 @@
 #include <dlfcn.h>
 #include <rccl/rccl.h>
 
-#include <functional>
 #include <map>
 #include <vector>
 
@@ -348,12 +347,9 @@ struct mdp_handle {
   bool critic_pre = true;
   float* apre_rows = nullptr;  // the replay rows those launches gathered (read contiguously by the step)
   float* cpre_rows = nullptr;
-  hipGraph_t round_graph = nullptr;
-  hipGraphExec_t round_exec = nullptr;
-  // mdp_train_step graphs (rollout + k rounds), one per k
-  std::map<int, hipGraphExec_t> step_exec;
-  // mdp_train_steps graphs: several consecutive steps as one graph, keyed by their round counts
-  std::map<std::vector<int>, hipGraphExec_t> multi_exec;
+  // every captured graph (captured_graph), keyed {kind (0 update round, 1 train step: rollout + k
+  // rounds, 2 group of consecutive steps), MATD3: every agent's update count mod the delay, the round counts}
+  std::map<std::vector<int>, hipGraphExec_t> graph_exec;
   int eager_steps = 0;
   // native data parallelism (mdp_dp_init): RCCL communicator of this rank
   ncclComm_t comm = nullptr;
@@ -412,17 +408,17 @@ struct mdp_handle {
   // and records, beta powers, stats and its optimizer's own sync area
   bool td3 = false;
   int td3_delay = 2;
-  float *theta2 = nullptr, *target2 = nullptr, *m2 = nullptr, *v2 = nullptr, *grad2 = nullptr;
-  float *slab2 = nullptr, *beta2 = nullptr;
-  double *stat2 = nullptr, *stats2 = nullptr;
-  uint32_t *ra_ctr2 = nullptr, *ticket2 = nullptr;
-  uint64_t* ra_part2 = nullptr;
+  struct Critic2 {
+    float *theta = nullptr, *target = nullptr, *m = nullptr, *v = nullptr, *grad = nullptr;
+    float *slab = nullptr, *beta = nullptr;
+    double *stat = nullptr, *stats = nullptr;
+    uint32_t *ticket = nullptr, *ctr = nullptr;
+    uint64_t* part = nullptr;
+  } c2;
   // updates of agent i since enable: committed once the launch or replay was
   // issued (td3_count), and as the launches being issued or captured see it (td3_work)
   int64_t td3_count[MDP_MAX_AGENTS] = {};
   int64_t td3_work[MDP_MAX_AGENTS] = {};
-  // graphs keyed by {kind (0 round, 1 step, 2 group), every agent's count mod d, the round counts}
-  std::map<std::vector<int>, hipGraphExec_t> td3_exec;
   // M3DDPG (mdp_minimax_enable): eps[i][j], and the debug buffers that receive
   // the moved actions of the critic / actor step (mdp_minimax_debug_adv)
   bool minimax = false;
@@ -434,12 +430,14 @@ struct mdp_handle {
   // optimizer launches' own sync area (one slot per approximated agent)
   bool approx = false;
   float apx_lambda = 1e-3f;
-  char* apx_buf = nullptr;
-  int64_t apx_region = 0, apx_obs_stride = 0;  // bytes
-  float *apx_slab = nullptr, *apx_beta = nullptr;
-  double* apx_stat = nullptr;
-  uint32_t *apx_ticket = nullptr, *apx_ctr = nullptr;
-  uint64_t* apx_part = nullptr;
+  struct Approx {
+    char* buf = nullptr;
+    int64_t region = 0, obs_stride = 0;  // bytes
+    float *slab = nullptr, *beta = nullptr;
+    double* stat = nullptr;
+    uint32_t *ticket = nullptr, *ctr = nullptr;
+    uint64_t* part = nullptr;
+  } apx;
   int64_t apx_count[MDP_MAX_AGENTS] = {};  // approximator steps of observer i so far
   int apx_pending = -1;  // observer whose gradient-only launch (mdp_approx_grad) the partials hold, or -1
 };
@@ -620,7 +618,7 @@ float* which_base(mdp_handle* h, int which, int* net) {
       return nullptr;
     }
     *net = 1;
-    float* const b[5] = {h->theta2, h->target2, h->m2, h->v2, h->grad2};
+    float* const b[5] = {h->c2.theta, h->c2.target, h->c2.m, h->c2.v, h->c2.grad};
     return b[which - MDP_CRITIC2];
   }
   int region;
@@ -698,6 +696,52 @@ std::vector<float> scatter_net(const mdp_handle* h, int agent, int net, const fl
     }
   }
   return buf;
+}
+
+// the inverse: the logical layout from the device block (the pad entries are dropped)
+void gather_net(const mdp_handle* h, int agent, int net, const float* block, float* dst) {
+  const NDesc& d = net ? h->L.topo.ag[agent].critic : h->L.topo.ag[agent].actor;
+  int64_t s = 0;
+  for (int t = 0; t < 6; ++t) {
+    int rows, cols;
+    logical_shape(h, agent, net, t, &rows, &cols);
+    for (int r = 0; r < rows; ++r, s += cols) {
+      const int dr = (net && t == 0) ? critic_w1_dev_row(h, agent, r) : r;
+      std::memcpy(dst + s, block + (d.t[t].off - d.off) + (int64_t)dr * d.t[t].cols, 4 * (int64_t)cols);
+    }
+  }
+}
+
+// agent's net in the param-space region at `base` (the arena's, the second
+// critic's, an observer's approximators') from / to the logical layout, synchronous
+int write_net(mdp_handle* h, float* base, int agent, int net, const float* src) {
+  const std::vector<float> buf = scatter_net(h, agent, net, src);
+  HIPCHK(h, hipMemcpyAsync(base + net_of(h, agent, net).off, buf.data(), 4 * buf.size(), hipMemcpyHostToDevice,
+                           h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  return 0;
+}
+
+int read_net(mdp_handle* h, const float* base, int agent, int net, float* dst) {
+  const NDesc& d = net_of(h, agent, net);
+  std::vector<float> buf(d.size);
+  HIPCHK(h, hipMemcpyAsync(buf.data(), base + d.off, 4 * buf.size(), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  gather_net(h, agent, net, buf.data(), dst);
+  return 0;
+}
+
+// the two beta powers (beta1^t, beta2^t) an optimizer's next step reads, synchronous
+int write_beta_powers(mdp_handle* h, float* dst, const float in2[2]) {
+  HIPCHK(h, hipMemcpyAsync(dst, in2, 8, hipMemcpyHostToDevice, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  return 0;
+}
+
+int read_beta_powers(mdp_handle* h, const float* src, float out2[2]) {
+  HIPCHK(h, hipMemcpyAsync(out2, src, 8, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  return 0;
 }
 
 int launch_make_index(mdp_handle* h, int count, int32_t* out) {
@@ -779,7 +823,7 @@ bool apx_agent(const mdp_handle* h, int agent) {
 }
 // param-space base of set k (mdp_approx_set) of observer's approximators
 float* apx_base(const mdp_handle* h, int observer, int k) {
-  return (float*)(h->apx_buf + observer * h->apx_obs_stride + k * h->apx_region);
+  return (float*)(h->apx.buf + observer * h->apx.obs_stride + k * h->apx.region);
 }
 
 int do_critic_grad(mdp_handle* h, int agent, const int32_t* idx, const float* u_tgt, int32_t* pf_out = nullptr,
@@ -885,26 +929,144 @@ int do_actor_grad(mdp_handle* h, int agent, const int32_t* idx, const float* u_a
   return 0;
 }
 
-// net 1: critic Adam (+ critic stats); net 0: actor Adam + Polyak of both nets (+ actor stats)
-ApplyArgs apply_args(mdp_handle* h, int agent, int net, float scale, bool tp = false) {
+// ---- the optimizer step of one net: reduce the partials, clip,
+// Adam, maybe Polyak.  An OptNet says where one net's optimizer state lives;
+// the three constructors below are the only places that know the arena, the
+// TD3 buffer and the approximator buffer apart.
+struct OptNet {
+  NDesc net, other;                        // the stepped net; the agent's other net (Polyak of both in the actor step)
+  float *theta, *target, *m, *v, *grad;    // param-space bases
+  const float* slab;                       // partial gradients [nwg][slab_stride]
+  int slab_stride;
+  float* beta;                             // this optimizer's beta powers
+  const double* slab_stat;                 // the gradient launch's records, the TD targets, the stats block
+  const double* y;
+  double* stats_out;
+  uint32_t* ticket;
+  uint32_t* ctr;                           // sync area of the optimizer launches: counters, partial norms, this net's slot
+  uint64_t* part;
+  int slot;
+  int net_id;                              // 2 * agent + net of the stepped net's shape
+  int polyak, stats_mode, bump_ctr;
+  bool own;                                // a net of the handle's arena (the xGMI exchange serves only those)
+};
+
+// what follows from the stepped net's shape alone (agent's actor, net 0, or critic, net 1)
+OptNet opt_shape(const mdp_handle* h, int agent, int net) {
   const ADesc& ag = h->L.topo.ag[agent];
+  OptNet o = {};
+  o.net = net ? ag.critic : ag.actor;
+  o.other = net ? ag.actor : ag.critic;
+  o.slab_stride = net ? h->L.slab_c : h->L.slab_a;
+  o.net_id = 2 * agent + net;
+  return o;
+}
+
+// a net of the arena.  net 1: critic Adam (+ critic stats); net 0: actor Adam +
+// Polyak of both nets (+ actor stats), and the noise counter advances
+OptNet opt_own(mdp_handle* h, int agent, int net) {
+  OptNet o = opt_shape(h, agent, net);
+  o.theta = h->theta;
+  o.target = h->target;
+  o.m = h->m;
+  o.v = h->v;
+  o.grad = h->grad;
+  o.slab = net ? h->slab_c : h->slab_a;
+  o.beta = h->beta + agent * 8 + net * 4;
+  o.slab_stat = net ? h->stat_c : h->stat_a;
+  o.y = h->y;
+  o.stats_out = h->stats + agent * 8;
+  o.ticket = &h->ctl->ticket[net];
+  o.ctr = h->ra_ctr;
+  o.part = h->ra_part;
+  o.slot = o.net_id;
+  o.polyak = net ? 0 : 1;
+  o.stats_mode = net ? 1 : 1 + topo_act_w(h->L.topo, agent);
+  o.bump_ctr = net ? 0 : 1;
+  o.own = true;
+  return o;
+}
+
+// MATD3's second critic of agent: the critic's shape, its state in the TD3
+// buffer (its own sync area, one slot per agent, and stats block; the TD targets
+// are the first critic's), no Polyak.  bump: 1 on a critic-only update, whose
+// last optimizer launch this is
+OptNet opt_critic2(mdp_handle* h, int agent, int bump) {
+  const mdp_handle::Critic2& c = h->c2;
+  OptNet o = opt_shape(h, agent, 1);
+  o.theta = c.theta;
+  o.target = c.target;
+  o.m = c.m;
+  o.v = c.v;
+  o.grad = c.grad;
+  o.slab = c.slab;
+  o.beta = c.beta + agent * 4;
+  o.slab_stat = c.stat;
+  o.y = h->y;
+  o.stats_out = c.stats + agent * 8;
+  o.ticket = c.ticket;
+  o.ctr = c.ctr;
+  o.part = c.part;
+  o.slot = agent;
+  o.polyak = 0;
+  o.stats_mode = 1;
+  o.bump_ctr = bump;
+  o.own = false;
+  return o;
+}
+
+// observer's approximator of agent j (pair p of do_approx_grad's launch): agent
+// j's actor shape, its state in the approximator buffer, no Polyak, no stats
+// (null records, TD targets and stats block).  The sync slot goes by j, the
+// slice of partials by p
+OptNet opt_approx(mdp_handle* h, int observer, int j, int p) {
+  const mdp_handle::Approx& x = h->apx;
+  OptNet o = opt_shape(h, j, 0);
+  o.theta = apx_base(h, observer, MDP_APX_NET);
+  o.target = apx_base(h, observer, MDP_APX_TARGET);
+  o.m = apx_base(h, observer, MDP_APX_M);
+  o.v = apx_base(h, observer, MDP_APX_V);
+  o.grad = apx_base(h, observer, MDP_APX_GRAD);
+  o.slab = x.slab + (int64_t)p * h->L.nwg * h->L.slab_a;
+  o.beta = x.beta + ((int64_t)observer * h->cfg.n_agents + j) * 4;
+  o.ticket = x.ticket;
+  o.ctr = x.ctr;
+  o.part = x.part;
+  o.slot = j;
+  o.polyak = 0;
+  o.stats_mode = 0;
+  o.bump_ctr = 0;
+  o.own = false;
+  return o;
+}
+
+// target <- pa target + pb theta (make_update_exp, maddpg.py:20-26)
+void polyak_coef(const mdp_handle* h, float* pa, float* pb) {
+  const double tau = (double)h->cfg.tau;
+  *pa = (float)(1.0 - tau);
+  *pb = (float)(1.0 - (1.0 - tau));
+}
+
+// prefix counts of `chunk`-parameter workgroups per tensor
+void chunk_table(const NDesc& d, int chunk, int* blk) {
+  blk[0] = 0;
+  for (int t = 0; t < 6; ++t) blk[t + 1] = blk[t] + (d.t[t].rows * d.t[t].cols + chunk - 1) / chunk;
+}
+
+// k_apply: the step from grad[] (already reduced / all-reduced)
+ApplyArgs apply_args(mdp_handle* h, const OptNet& o, float scale) {
   ApplyArgs a;
-  a.net = net ? ag.critic : ag.actor;
-  a.other = net ? ag.actor : ag.critic;
-  a.theta = h->theta;
-  a.target = h->target;
-  a.m = h->m;
-  a.v = h->v;
-  a.grad = h->grad;
-  auto chunks = [](const NDesc& d, int* blk) {
-    blk[0] = 0;
-    for (int t = 0; t < 6; ++t)
-      blk[t + 1] = blk[t] + (d.t[t].rows * d.t[t].cols + MDP_APPLY_CHUNK - 1) / MDP_APPLY_CHUNK;
-  };
-  chunks(a.net, a.blk);
-  chunks(a.other, a.oblk);
+  a.net = o.net;
+  a.other = o.other;
+  a.theta = o.theta;
+  a.target = o.target;
+  a.m = o.m;
+  a.v = o.v;
+  a.grad = o.grad;
+  chunk_table(a.net, MDP_APPLY_CHUNK, a.blk);
+  chunk_table(a.other, MDP_APPLY_CHUNK, a.oblk);
   a.slab = nullptr;
-  a.slab_stride = net ? h->L.slab_c : h->L.slab_a;
+  a.slab_stride = o.slab_stride;
   a.nwg = h->L.nwg;
   a.scale = scale;
   a.clip = h->cfg.grad_clip;
@@ -912,29 +1074,56 @@ ApplyArgs apply_args(mdp_handle* h, int agent, int net, float scale, bool tp = f
   a.b1 = h->cfg.adam_b1;
   a.b2 = h->cfg.adam_b2;
   a.eps = h->cfg.adam_eps;
-  a.beta = h->beta + agent * 8 + net * 4;
-  a.polyak = net ? 0 : 1;
-  const double tau = (double)h->cfg.tau;
-  a.pa = (float)(1.0 - tau);
-  a.pb = (float)(1.0 - (1.0 - tau));
-  a.stats_mode = net ? 1 : 1 + topo_act_w(h->L.topo, agent);
-  a.slab_stat = net ? h->stat_c : h->stat_a;
-  a.y = h->y;
+  a.beta = o.beta;
+  a.polyak = o.polyak;
+  polyak_coef(h, &a.pa, &a.pb);
+  a.stats_mode = o.stats_mode;
+  a.slab_stat = o.slab_stat;
+  a.y = o.y;
   a.B = h->cfg.batch_size;
   a.reg = h->cfg.actor_reg;
-  a.stats_out = h->stats + agent * 8;
-  a.ticket = &h->ctl->ticket[net];
+  a.stats_out = o.stats_out;
+  a.ticket = o.ticket;
   a.ctl = h->ctl;
-  a.bump_ctr = net ? 0 : 1;
+  a.bump_ctr = o.bump_ctr;
   return a;
 }
 
-int do_apply(mdp_handle* h, int agent, int net, bool from_slab, float scale) {
-  (void)from_slab;
-  const ApplyArgs a = apply_args(h, agent, net, scale);
-  ProfScope p(h, MDP_K_APPLY);
-  HIPCHK(h, mdp_launch_apply(a, h->stream));
-  return 0;
+// k_reduce_apply: the step from the partials, its chunk workgroups handshaking in the net's sync slot
+FusedApplyArgs fused_args(mdp_handle* h, const OptNet& o, float scale = 1.0f) {
+  FusedApplyArgs f;
+  f.ap = apply_args(h, o, scale);
+  f.ap.slab = o.slab;
+  chunk_table(f.ap.net, MDP_RA_CHUNK, f.rblk);
+  f.sync_ctr = o.ctr + (int64_t)o.slot * 8 * 32;
+  f.done_ctr = f.sync_ctr + 6 * 32;
+  f.sync_part = o.part + (int64_t)o.slot * 6 * MDP_RA_MAXCH * 2;
+  f.phase = 0;
+  f.xd = nullptr;
+  f.net_id = o.net_id;
+  f.xstep = nullptr;
+  f.wstat = nullptr;
+  f.pf_count = 0;
+  f.pf_out = nullptr;
+  f.pf_ctl = h->ctl;
+  return f;
+}
+
+// k_reduce: the partials summed into grad[]
+ReduceArgs reduce_args(mdp_handle* h, const OptNet& o) {
+  ReduceArgs a;
+  a.slab = o.slab;
+  a.nwg = h->L.nwg;
+  a.slab_stride = o.slab_stride;
+  a.grad = o.grad;
+  a.off = o.net.off;
+  a.size = o.net.size;
+  a.beta = o.beta;
+  a.b1 = h->cfg.adam_b1;
+  a.b2 = h->cfg.adam_b2;
+  a.ctl = h->ctl;
+  a.bump_ctr = o.bump_ctr;
+  return a;
 }
 
 // batch reduction + clip + Adam (+ Polyak, stats, beta advance) in one launch
@@ -947,36 +1136,21 @@ bool reduce_apply_ok(const mdp_handle* h, int agent, int net) {
   return mdp_ra_fits(h->L.topo, agent, net, h->ra_cap);
 }
 
-FusedApplyArgs fused_args_for(mdp_handle* h, int agent, int net, bool tp = false) {
-  FusedApplyArgs f;
-  f.ap = apply_args(h, agent, net, 1.0f, tp);
-  f.ap.slab = net ? h->slab_c : h->slab_a;
-  f.rblk[0] = 0;
-  for (int t = 0; t < 6; ++t)
-    f.rblk[t + 1] = f.rblk[t] + (f.ap.net.t[t].rows * f.ap.net.t[t].cols + MDP_RA_CHUNK - 1) / MDP_RA_CHUNK;
-  const int g = agent * 2 + net;
-  f.sync_ctr = h->ra_ctr + (int64_t)g * 8 * 32;
-  f.done_ctr = f.sync_ctr + 6 * 32;
-  f.sync_part = h->ra_part + (int64_t)g * 6 * MDP_RA_MAXCH * 2;
-  f.phase = 0;
-  f.xd = nullptr;
-  f.net_id = g;
-  f.xstep = nullptr;
-  f.wstat = nullptr;
-  f.pf_count = 0;
-  f.pf_out = nullptr;
-  f.pf_ctl = h->ctl;
-  return f;
-}
-
 // phase 3: reduce + xGMI exchange with every rank + step x 1/G (one launch)
-void set_xchg(mdp_handle* h, FusedApplyArgs& f, int agent, int net) {
+void set_xchg(mdp_handle* h, FusedApplyArgs& f) {
   f.phase = 3;
   f.ap.scale = 1.0f / (float)h->dp_world;
   f.xd = h->xd_dev;
-  f.net_id = 2 * agent + net;
   f.xstep = h->ctl->xstep + f.net_id;
   f.wstat = h->xw_stats ? &h->ctl->xw_ticks : nullptr;
+}
+
+// every captured graph goes (what they captured no longer holds); reset_eager:
+// the next round and the next training step run eagerly again before a capture
+void destroy_graphs(mdp_handle* h, bool reset_eager) {
+  for (auto& kv : h->graph_exec) (void)hipGraphExecDestroy(kv.second);
+  h->graph_exec.clear();
+  if (reset_eager) h->eager_steps = h->eager_rounds = 0;
 }
 
 void xgmi_release(mdp_handle* h) {
@@ -994,36 +1168,42 @@ void xgmi_release(mdp_handle* h) {
   h->x_rank = 0;
 }
 
-// pf_out / pf_count: a piece of the next round's index draw rides in this launch
-int do_reduce_apply(mdp_handle* h, int agent, int net, int32_t* pf_out = nullptr, int pf_count = 0) {
-  FusedApplyArgs f = fused_args_for(h, agent, net);
-  if (pf_out && pf_count > 0) {
-    f.pf_out = pf_out;
-    f.pf_count = pf_count;
-  }
-  if (h->p2p) set_xchg(h, f, agent, net);
-  ProfScope p(h, MDP_K_REDUCE_APPLY);
-  HIPCHK(h, mdp_launch_reduce_apply(f, h->stream));
-  return 0;
-}
-
-int do_reduce(mdp_handle* h, int agent, int net) {
-  const NDesc& d = net_of(h, agent, net);
-  ReduceArgs a;
-  a.slab = net ? h->slab_c : h->slab_a;
-  a.nwg = h->L.nwg;
-  a.slab_stride = net ? h->L.slab_c : h->L.slab_a;
-  a.grad = h->grad;
-  a.off = d.off;
-  a.size = d.size;
-  a.beta = h->beta + agent * 8 + net * 4;
-  a.b1 = h->cfg.adam_b1;
-  a.b2 = h->cfg.adam_b2;
-  a.ctl = h->ctl;
-  a.bump_ctr = net ? 0 : 1;
+int launch_reduce(mdp_handle* h, const OptNet& o) {
+  const ReduceArgs a = reduce_args(h, o);
   ProfScope p(h, MDP_K_REDUCE);
   HIPCHK(h, mdp_launch_reduce(a, h->stream));
   return 0;
+}
+
+int launch_apply(mdp_handle* h, const OptNet& o, float scale) {
+  const ApplyArgs a = apply_args(h, o, scale);
+  ProfScope p(h, MDP_K_APPLY);
+  HIPCHK(h, mdp_launch_apply(a, h->stream));
+  return 0;
+}
+
+// one net's optimizer step: one k_reduce_apply launch (fused), or k_reduce +
+// k_apply.  pf_out / pf_count: a piece of the next round's index draw rides in
+// the fused launch (the handle's own nets)
+int opt_step(mdp_handle* h, const OptNet& o, bool fused, float scale, int32_t* pf_out = nullptr, int pf_count = 0) {
+  if (fused) {
+    FusedApplyArgs f = fused_args(h, o, scale);
+    if (pf_out && pf_count > 0) {
+      f.pf_out = pf_out;
+      f.pf_count = pf_count;
+    }
+    if (h->p2p && o.own) set_xchg(h, f);
+    ProfScope p(h, MDP_K_REDUCE_APPLY);
+    HIPCHK(h, mdp_launch_reduce_apply(f, h->stream));
+    return 0;
+  }
+  const int rc = launch_reduce(h, o);
+  if (rc) return rc;
+  OptNet a = o;
+  // k_reduce advanced the noise counter and k_apply never reads the field: the
+  // second critic's is cleared, the own actor's rides along as it always has
+  if (!o.own) a.bump_ctr = 0;
+  return launch_apply(h, a, scale);
 }
 
 // ---- RCCL, loaded on first use (the library has no link-time RCCL dependency)
@@ -1119,80 +1299,25 @@ int do_update_dp(mdp_handle* h, int agent, const int32_t* idx, const float* u_tg
                  int32_t* pf_out, int post_prev, int pre_next, const int32_t* pre_idx, const DrawPieces& dp) {
   const float scale = 1.0f / (float)h->dp_world;
   const bool pre = actor_pre_ok(h, agent);
+  const OptNet critic = opt_own(h, agent, 1), actor = opt_own(h, agent, 0);
   int rc;
   if (h->p2p) {  // the exchange lives inside the optimizer launch: same 4 launches as one GPU
     if ((rc = do_critic_grad(h, agent, idx, u_tgt, pf_out, false, pre, u_act, post_prev, dp.n_grad))) return rc;
-    if ((rc = do_reduce_apply(h, agent, 1, dp.out, dp.n_critic))) return rc;
+    if ((rc = opt_step(h, critic, true, scale, dp.out, dp.n_critic))) return rc;
     if ((rc = do_actor_grad(h, agent, idx, u_act, false, pre, pre_next, pre_idx))) return rc;
-    return do_reduce_apply(h, agent, 0, dp.out ? dp.out + dp.n_critic : nullptr, dp.n_actor);
+    return opt_step(h, actor, true, scale, dp.out ? dp.out + dp.n_critic : nullptr, dp.n_actor);
   }
   if ((rc = do_critic_grad(h, agent, idx, u_tgt, pf_out, false, pre, u_act, post_prev, dp.n_grad))) return rc;
-  if ((rc = do_reduce(h, agent, 1))) return rc;
+  if ((rc = launch_reduce(h, critic))) return rc;
   if ((rc = dp_allreduce(h, agent, 1))) return rc;
-  if ((rc = do_apply(h, agent, 1, false, scale))) return rc;
+  if ((rc = launch_apply(h, critic, scale))) return rc;
   if ((rc = do_actor_grad(h, agent, idx, u_act, false, pre, pre_next, pre_idx))) return rc;
-  if ((rc = do_reduce(h, agent, 0))) return rc;
+  if ((rc = launch_reduce(h, actor))) return rc;
   if ((rc = dp_allreduce(h, agent, 0))) return rc;
-  return do_apply(h, agent, 0, false, scale);
+  return launch_apply(h, actor, scale);
 }
 
 // ---- MATD3
-// critic 2's optimizer step: critic 1's arguments with every pointer swapped
-// into the TD3 buffer (its own sync area, no Polyak, its own stats block)
-FusedApplyArgs td3_fused_args(mdp_handle* h, int agent, int bump) {
-  FusedApplyArgs f = fused_args_for(h, agent, 1);
-  ApplyArgs& a = f.ap;
-  a.theta = h->theta2;
-  a.target = h->target2;
-  a.m = h->m2;
-  a.v = h->v2;
-  a.grad = h->grad2;
-  a.slab = h->slab2;
-  a.beta = h->beta2 + agent * 4;
-  a.polyak = 0;
-  a.slab_stat = h->stat2;
-  a.y = h->y;
-  a.stats_out = h->stats2 + agent * 8;
-  a.ticket = h->ticket2;
-  a.bump_ctr = bump;
-  f.sync_ctr = h->ra_ctr2 + (int64_t)agent * 8 * 32;
-  f.done_ctr = f.sync_ctr + 6 * 32;
-  f.sync_part = h->ra_part2 + (int64_t)agent * 6 * MDP_RA_MAXCH * 2;
-  return f;
-}
-
-int td3_step2(mdp_handle* h, int agent, bool fused, int bump) {
-  const FusedApplyArgs f = td3_fused_args(h, agent, bump);
-  if (fused) {
-    ProfScope p(h, MDP_K_REDUCE_APPLY);
-    HIPCHK(h, mdp_launch_reduce_apply(f, h->stream));
-    return 0;
-  }
-  const NDesc& d = net_of(h, agent, 1);
-  ReduceArgs r;
-  r.slab = h->slab2;
-  r.nwg = h->L.nwg;
-  r.slab_stride = h->L.slab_c;
-  r.grad = h->grad2;
-  r.off = d.off;
-  r.size = d.size;
-  r.beta = f.ap.beta;
-  r.b1 = h->cfg.adam_b1;
-  r.b2 = h->cfg.adam_b2;
-  r.ctl = h->ctl;
-  r.bump_ctr = bump;
-  {
-    ProfScope p(h, MDP_K_REDUCE);
-    HIPCHK(h, mdp_launch_reduce(r, h->stream));
-  }
-  ApplyArgs a = f.ap;
-  a.slab = nullptr;
-  a.bump_ctr = 0;
-  ProfScope p(h, MDP_K_APPLY);
-  HIPCHK(h, mdp_launch_apply(a, h->stream));
-  return 0;
-}
-
 // agent's k-th update since enable: the twin critic launch, both critics'
 // optimizer steps, and every td3_delay-th time the actor step + Polyak of all
 // three targets.  A critic-only update advances the noise counter in critic
@@ -1208,32 +1333,23 @@ int do_update_td3(mdp_handle* h, int agent, const int32_t* idx, const float* u_t
     while (t.group > 1 && lds_critic_twin_bytes(h->L.topo, t.group) > MDP_LDS_BUDGET) --t.group;
     const int lds = lds_critic_twin_bytes(h->L.topo, t.group);
     if (lds > MDP_LDS_BUDGET) return fail(h, "MATD3 critic step does not fit in LDS");
-    t.theta2 = h->theta2;
-    t.target2 = h->target2;
-    t.slab2 = h->slab2;
-    t.slab_stat2 = h->stat2;
+    t.theta2 = h->c2.theta;
+    t.target2 = h->c2.target;
+    t.slab2 = h->c2.slab;
+    t.slab_stat2 = h->c2.stat;
     ProfScope p(h, MDP_K_CRITIC_GRAD);
     HIPCHK(h, mdp_launch_critic_grad_twin(t, h->L.topo.H, lds, h->stream));
   }
-  if (fused) {
-    if ((rc = do_reduce_apply(h, agent, 1))) return rc;
-  } else {
-    if ((rc = do_reduce(h, agent, 1))) return rc;
-    if ((rc = do_apply(h, agent, 1, false, 1.0f))) return rc;
-  }
-  if ((rc = td3_step2(h, agent, fused, actor_due ? 0 : 1))) return rc;
+  if ((rc = opt_step(h, opt_own(h, agent, 1), fused, 1.0f))) return rc;
+  if ((rc = opt_step(h, opt_critic2(h, agent, actor_due ? 0 : 1), fused, 1.0f))) return rc;
   if (!actor_due) return 0;
   if ((rc = do_actor_grad(h, agent, idx, u_act))) return rc;
-  if (fused) {
-    if ((rc = do_reduce_apply(h, agent, 0))) return rc;
-  } else {
-    if ((rc = do_reduce(h, agent, 0))) return rc;
-    if ((rc = do_apply(h, agent, 0, false, 1.0f))) return rc;
-  }
+  if ((rc = opt_step(h, opt_own(h, agent, 0), fused, 1.0f))) return rc;
   const NDesc& d = net_of(h, agent, 1);
-  const ApplyArgs a = apply_args(h, agent, 0, 1.0f);
+  float pa, pb;
+  polyak_coef(h, &pa, &pb);
   ProfScope p(h, MDP_K_APPLY);
-  HIPCHK(h, mdp_launch_polyak(h->target2 + d.off, h->theta2 + d.off, d.size, a.pa, a.pb, h->ctl, h->stream));
+  HIPCHK(h, mdp_launch_polyak(h->c2.target + d.off, h->c2.theta + d.off, d.size, pa, pb, h->ctl, h->stream));
   return 0;
 }
 
@@ -1252,56 +1368,12 @@ int do_approx_grad(mdp_handle* h, int observer, const int32_t* idx) {
   a.idx = idx;
   a.inv_b = 1.0f / (float)a.B;
   a.lambda = h->apx_lambda;
-  a.slab = h->apx_slab;
+  a.slab = h->apx.slab;
   a.slab_stride = h->L.slab_a;
-  a.slab_stat = h->apx_stat + (int64_t)observer * h->cfg.n_agents * h->L.nwg * 8;
+  a.slab_stat = h->apx.stat + (int64_t)observer * h->cfg.n_agents * h->L.nwg * 8;
   a.topo = h->L.topo;
   ProfScope p(h, MDP_K_ACTOR_GRAD);
   HIPCHK(h, mdp_launch_approx_grad(a, h->L.topo.H, lds_approx_bytes(h->L.topo), h->stream));
-  return 0;
-}
-
-// the optimizer step of phi_observer^j (pair p of the launch above): agent j's
-// actor step with every pointer in the approximator buffer, no Polyak, no stats
-FusedApplyArgs apx_fused_args(mdp_handle* h, int observer, int j, int p) {
-  FusedApplyArgs f = fused_args_for(h, j, 0);
-  ApplyArgs& a = f.ap;
-  a.theta = apx_base(h, observer, MDP_APX_NET);
-  a.target = apx_base(h, observer, MDP_APX_TARGET);
-  a.m = apx_base(h, observer, MDP_APX_M);
-  a.v = apx_base(h, observer, MDP_APX_V);
-  a.grad = apx_base(h, observer, MDP_APX_GRAD);
-  a.slab = h->apx_slab + (int64_t)p * h->L.nwg * h->L.slab_a;
-  a.beta = h->apx_beta + ((int64_t)observer * h->cfg.n_agents + j) * 4;
-  a.polyak = 0;
-  a.stats_mode = 0;
-  a.slab_stat = nullptr;
-  a.y = nullptr;
-  a.stats_out = nullptr;
-  a.ticket = h->apx_ticket;
-  a.bump_ctr = 0;
-  f.sync_ctr = h->apx_ctr + (int64_t)j * 8 * 32;
-  f.done_ctr = f.sync_ctr + 6 * 32;
-  f.sync_part = h->apx_part + (int64_t)j * 6 * MDP_RA_MAXCH * 2;
-  return f;
-}
-
-int apx_reduce(mdp_handle* h, int observer, int j, int p, float* beta) {
-  const NDesc& d = net_of(h, j, 0);
-  ReduceArgs r;
-  r.slab = h->apx_slab + (int64_t)p * h->L.nwg * h->L.slab_a;
-  r.nwg = h->L.nwg;
-  r.slab_stride = h->L.slab_a;
-  r.grad = apx_base(h, observer, MDP_APX_GRAD);
-  r.off = d.off;
-  r.size = d.size;
-  r.beta = beta;
-  r.b1 = h->cfg.adam_b1;
-  r.b2 = h->cfg.adam_b2;
-  r.ctl = h->ctl;
-  r.bump_ctr = 0;
-  ProfScope ps(h, MDP_K_REDUCE);
-  HIPCHK(h, mdp_launch_reduce(r, h->stream));
   return 0;
 }
 
@@ -1311,24 +1383,15 @@ int do_approx_opt(mdp_handle* h, int observer) {
   int p = 0;
   for (int j = 0; j < h->cfg.n_agents; ++j) {
     if (j == observer) continue;
-    const FusedApplyArgs f = apx_fused_args(h, observer, j, p);
-    if (h->fused_apply && reduce_apply_ok(h, j, 0)) {
-      ProfScope ps(h, MDP_K_REDUCE_APPLY);
-      HIPCHK(h, mdp_launch_reduce_apply(f, h->stream));
-    } else {
-      int rc;
-      if ((rc = apx_reduce(h, observer, j, p, f.ap.beta))) return rc;
-      ApplyArgs a = f.ap;
-      a.slab = nullptr;
-      ProfScope ps(h, MDP_K_APPLY);
-      HIPCHK(h, mdp_launch_apply(a, h->stream));
-    }
+    const int rc = opt_step(h, opt_approx(h, observer, j, p), h->fused_apply && reduce_apply_ok(h, j, 0), 1.0f);
+    if (rc) return rc;
     ++p;
   }
-  const ApplyArgs a = apply_args(h, observer, 0, 1.0f);
+  float pa, pb;
+  polyak_coef(h, &pa, &pb);
   ProfScope ps(h, MDP_K_APPLY);
-  HIPCHK(h, mdp_launch_polyak(apx_base(h, observer, MDP_APX_TARGET), apx_base(h, observer, MDP_APX_NET), h->L.PT, a.pa,
-                              a.pb, h->ctl, h->stream));
+  HIPCHK(h, mdp_launch_polyak(apx_base(h, observer, MDP_APX_TARGET), apx_base(h, observer, MDP_APX_NET), h->L.PT, pa,
+                              pb, h->ctl, h->stream));
   return 0;
 }
 
@@ -1352,19 +1415,10 @@ int do_update(mdp_handle* h, int agent, const int32_t* idx, const float* u_tgt, 
   const bool fused = h->fused_apply && reduce_apply_ok(h, agent, 0) && reduce_apply_ok(h, agent, 1);
   const bool pre = actor_pre_ok(h, agent);
   if ((rc = do_critic_grad(h, agent, idx, u_tgt, pf_out, false, pre, u_act, post_prev, dp.n_grad))) return rc;
-  if (fused) {
-    if ((rc = do_reduce_apply(h, agent, 1, dp.out, dp.n_critic))) return rc;
-  } else {
-    if ((rc = do_reduce(h, agent, 1))) return rc;
-    if ((rc = do_apply(h, agent, 1, false, 1.0f))) return rc;
-  }
+  if ((rc = opt_step(h, opt_own(h, agent, 1), fused, 1.0f, dp.out, dp.n_critic))) return rc;
   if ((rc = do_actor_grad(h, agent, idx, u_act, false, pre, pre_next, pre_idx))) return rc;
-  if (fused) {
-    if ((rc = do_reduce_apply(h, agent, 0, dp.out ? dp.out + dp.n_critic : nullptr, dp.n_actor))) return rc;
-  } else {
-    if ((rc = do_reduce(h, agent, 0))) return rc;
-    if ((rc = do_apply(h, agent, 0, false, 1.0f))) return rc;
-  }
+  if ((rc = opt_step(h, opt_own(h, agent, 0), fused, 1.0f, dp.out ? dp.out + dp.n_critic : nullptr, dp.n_actor)))
+    return rc;
   // inferred policies: the approximators step last, so every target this update
   // read was the one standing at its start
   if (apx_agent(h, agent)) return do_approx_step(h, agent, idx);
@@ -1397,13 +1451,14 @@ bool tp_ok(const mdp_handle* h) {
 // upd_ctr + agent)
 FusedApplyArgs tp_args(mdp_handle* h, int agent, int net) {
   const int64_t nwg = h->L.nwg;
-  FusedApplyArgs f = fused_args_for(h, agent, net, true);
-  f.ap.slab = net ? h->slab_c + agent * nwg * h->L.slab_c : h->slab_a + agent * nwg * h->L.slab_a;
-  f.ap.slab_stat = (net ? h->stat_c : h->stat_a) + agent * nwg * 8;
-  f.ap.y = h->y + (int64_t)agent * h->cfg.batch_size;
-  f.ap.polyak = 1;
+  OptNet o = opt_own(h, agent, net);
+  o.slab += agent * nwg * o.slab_stride;
+  o.slab_stat += agent * nwg * 8;
+  o.y += (int64_t)agent * h->cfg.batch_size;
+  o.polyak = 1;
+  o.bump_ctr = (net == 0 && agent == 0) ? h->cfg.n_agents : 0;
+  FusedApplyArgs f = fused_args(h, o);
   for (int t = 0; t < 7; ++t) f.ap.oblk[t] = 0;
-  f.ap.bump_ctr = (net == 0 && agent == 0) ? h->cfg.n_agents : 0;
   return f;
 }
 
@@ -1429,7 +1484,7 @@ int tp_setup(mdp_handle* h) {
         f.phase = ph;
         if (ph == 2) f.ap.scale = 1.0f / (float)h->dp_world;
         if (ph == 3) {
-          if (h->p2p) set_xchg(h, f, i, net);
+          if (h->p2p) set_xchg(h, f);
           else f.phase = 0;  // unused list
         }
         list.push_back(f);
@@ -1461,7 +1516,7 @@ int tp_setup(mdp_handle* h) {
         f.ap.bump_ctr = (net == 0 && i == n - 1) ? n : 0;
         f.phase = pair_phase[pp];
         if (pp == 2) {
-          if (h->p2p) set_xchg(h, f, i, net);
+          if (h->p2p) set_xchg(h, f);
           else f.phase = 0;  // unused list
         }
         list.push_back(f);
@@ -1625,8 +1680,9 @@ int tp_round_general(mdp_handle* h, const int32_t* idx, const float* u_tgt, cons
     ProfScope p(h, MDP_K_APPLY, h->tp_fits[2]);
     return launch_tp_batch(h, 2);
   }
-  const ApplyArgs a = apply_args(h, 0, 0, 1.0f);
-  HIPCHK(h, mdp_launch_polyak(h->target, h->theta, h->L.PT, a.pa, a.pb, h->ctl, h->stream));
+  float pa, pb;
+  polyak_coef(h, &pa, &pb);
+  HIPCHK(h, mdp_launch_polyak(h->target, h->theta, h->L.PT, pa, pb, h->ctl, h->stream));
   return 0;
 }
 
@@ -1772,6 +1828,11 @@ const char* kPerNoDp = "prioritized replay runs on one GPU in strict mode: no da
 const char* kTd3NoDp = "MATD3 (mdp_td3_enable) runs on one GPU in strict mode: no data-parallel exchange";
 const char* kMmNoDp = "M3DDPG (mdp_minimax_enable) runs on one GPU in strict mode: no data-parallel exchange";
 
+// an optimizer's own sync area for one net per agent (mdp_ra_sync_bytes holds the
+// arena's two): per slot 8 counters x 128 B, then per slot [6][MDP_RA_MAXCH][2] tagged words
+const int64_t kSyncCtrBytes = (int64_t)MDP_MAX_AGENTS * 8 * 128;
+const int64_t kSyncPartBytes = (int64_t)MDP_MAX_AGENTS * 6 * MDP_RA_MAXCH * 16;
+
 // byte offsets inside the caller's TD3 buffer
 struct Td3Layout {
   int64_t theta, target, m, v, grad, slab, stat, beta, stats, ticket, ctr, part, total;
@@ -1794,8 +1855,8 @@ Td3Layout td3_layout(const mdp_config& c, const Layout& L) {
   t.beta = take(4 * 4 * (int64_t)c.n_agents);
   t.stats = take(8 * 8 * (int64_t)c.n_agents);
   t.ticket = take(256);
-  t.ctr = take((int64_t)MDP_MAX_AGENTS * 8 * 128);          // per agent 8 counters x 128 B (mdp_ra_sync_bytes)
-  t.part = take((int64_t)MDP_MAX_AGENTS * 6 * MDP_RA_MAXCH * 16);
+  t.ctr = take(kSyncCtrBytes);  // one slot per agent
+  t.part = take(kSyncPartBytes);
   t.total = o;
   return t;
 }
@@ -1821,10 +1882,65 @@ ApxLayout apx_layout(const mdp_config& c, const Layout& L) {
   t.stat = take(8 * 8 * n * n * L.nwg);
   t.beta = take(4 * 4 * n * n);
   t.ticket = take(256);
-  t.ctr = take((int64_t)MDP_MAX_AGENTS * 8 * 128);  // per approximated agent 8 counters x 128 B
-  t.part = take((int64_t)MDP_MAX_AGENTS * 6 * MDP_RA_MAXCH * 16);
+  t.ctr = take(kSyncCtrBytes);  // one slot per approximated agent
+  t.part = take(kSyncPartBytes);
   t.total = o;
   return t;
+}
+
+// ---- host counters and the graph cache of the training entry points
+// MATD3's host counters: the launches about to be issued or captured count from
+// the committed state; commit_rounds after they (or a graph replay of them) went out
+void td3_begin(mdp_handle* h) {
+  for (int i = 0; i < MDP_MAX_AGENTS; ++i) h->td3_work[i] = h->td3_count[i];
+}
+// the host-side counts of `rounds` whole rounds that went out: the approximators'
+// step counts (inferred policies) and MATD3's update counts; a plain handle has neither
+void commit_rounds(mdp_handle* h, int rounds) {
+  if (h->approx && rounds > 0) {  // inferred policies: every observer's pairs stepped once per round
+    for (int i = 0; i < h->cfg.n_agents; ++i)
+      if (apx_agent(h, i)) h->apx_count[i] += rounds;
+    h->apx_pending = -1;
+  }
+  if (!h->td3) return;
+  for (int i = 0; i < h->cfg.n_agents; ++i) h->td3_count[i] += rounds;
+}
+// key of a captured graph.  With MATD3 what is captured depends on which agents
+// are due for an actor step: every agent's committed count mod the delay
+std::vector<int> graph_key(const mdp_handle* h, int kind, const std::vector<int>& ks) {
+  std::vector<int> key{kind};
+  if (h->td3)
+    for (int i = 0; i < h->cfg.n_agents; ++i) key.push_back((int)(h->td3_count[i] % h->td3_delay));
+  key.insert(key.end(), ks.begin(), ks.end());
+  return key;
+}
+// the graph of `body`'s launches under `key`, captured on first use (counting from the committed state)
+template <class Body>
+int captured_graph(mdp_handle* h, const std::vector<int>& key, Body body, hipGraphExec_t* out) {
+  auto it = h->graph_exec.find(key);
+  if (it != h->graph_exec.end()) {
+    *out = it->second;
+    return 0;
+  }
+  td3_begin(h);
+  HIPCHK(h, hipStreamBeginCapture(h->stream, hipStreamCaptureModeThreadLocal));
+  h->capturing = true;
+  const int rc = body();
+  h->capturing = false;
+  hipGraph_t g = nullptr;
+  const hipError_t e = hipStreamEndCapture(h->stream, &g);
+  if (rc) {
+    if (g) (void)hipGraphDestroy(g);
+    return rc;
+  }
+  if (e != hipSuccess) return fail(h, "hipStreamEndCapture", e);
+  hipGraphExec_t x = nullptr;
+  const hipError_t ei = hipGraphInstantiate(&x, g, nullptr, nullptr, 0);
+  (void)hipGraphDestroy(g);
+  if (ei != hipSuccess) return fail(h, "hipGraphInstantiate", ei);
+  h->graph_exec.emplace(key, x);
+  *out = x;
+  return 0;
 }
 
 }  // namespace
@@ -1986,13 +2102,9 @@ int mdp_destroy(mdp_handle* h) {
   if (h->tp_list) (void)hipFree(h->tp_list);
   for (int k = 0; k < MDP_K_COUNT; ++k)
     for (auto e : h->ev[k]) (void)hipEventDestroy(e);
-  if (h->round_exec) (void)hipGraphExecDestroy(h->round_exec);
+  destroy_graphs(h, true);
   if (h->comm) (void)rccl().destroy(h->comm);
   xgmi_release(h);
-  for (auto& kv : h->step_exec) (void)hipGraphExecDestroy(kv.second);
-  for (auto& kv : h->multi_exec) (void)hipGraphExecDestroy(kv.second);
-  for (auto& kv : h->td3_exec) (void)hipGraphExecDestroy(kv.second);
-  if (h->round_graph) (void)hipGraphDestroy(h->round_graph);
   if (h->own_stream && h->stream) (void)hipStreamDestroy(h->stream);
   delete h;
   return 0;
@@ -2072,14 +2184,9 @@ int mdp_set_params(mdp_handle* h, int32_t agent, int32_t which, const float* src
   int net;
   float* base = which_base(h, which, &net);
   if (!base) return -1;
-  const NDesc& d = net_of(h, agent, net);
   if (n != net_floats(h, agent, net)) return fail(h, "param count mismatch");
   h->started = true;
-  const std::vector<float> buf = scatter_net(h, agent, net, src);
-  float* dst = base + d.off;
-  HIPCHK(h, hipMemcpyAsync(dst, buf.data(), 4 * buf.size(), hipMemcpyHostToDevice, h->stream));
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  return 0;
+  return write_net(h, base, agent, net, src);
 }
 
 int mdp_get_params(mdp_handle* h, int32_t agent, int32_t which, float* dst, int64_t n) {
@@ -2087,40 +2194,20 @@ int mdp_get_params(mdp_handle* h, int32_t agent, int32_t which, float* dst, int6
   int net;
   const float* base = which_base(h, which, &net);
   if (!base) return -1;
-  const NDesc& d = net_of(h, agent, net);
   if (n != net_floats(h, agent, net)) return fail(h, "param count mismatch");
-  std::vector<float> buf(d.size);
-  const float* src = base + d.off;
-  HIPCHK(h, hipMemcpyAsync(buf.data(), src, 4 * buf.size(), hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  int64_t s = 0;
-  for (int t = 0; t < 6; ++t) {
-    int rows, cols;
-    logical_shape(h, agent, net, t, &rows, &cols);
-    for (int r = 0; r < rows; ++r, s += cols) {
-      const int dr = (net && t == 0) ? critic_w1_dev_row(h, agent, r) : r;
-      std::memcpy(dst + s, buf.data() + (d.t[t].off - d.off) + (int64_t)dr * d.t[t].cols, 4 * (int64_t)cols);
-    }
-  }
-  return 0;
+  return read_net(h, base, agent, net, dst);
 }
 
 int mdp_get_beta_powers(mdp_handle* h, int32_t agent, int32_t net, float out2[2]) {
   if (bad_agent(h, agent)) return -1;
   if (net == 2 && !h->td3) return fail(h, "mdp_get_beta_powers: net 2 (the second critic) needs MATD3 (mdp_td3_enable)");
-  const float* src = net == 2 ? h->beta2 + agent * 4 : h->beta + agent * 8 + (net ? 4 : 0);
-  HIPCHK(h, hipMemcpyAsync(out2, src, 8, hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  return 0;
+  return read_beta_powers(h, net == 2 ? h->c2.beta + agent * 4 : h->beta + agent * 8 + (net ? 4 : 0), out2);
 }
 
 int mdp_set_beta_powers(mdp_handle* h, int32_t agent, int32_t net, const float in2[2]) {
   if (bad_agent(h, agent)) return -1;
   if (net == 2 && !h->td3) return fail(h, "mdp_set_beta_powers: net 2 (the second critic) needs MATD3 (mdp_td3_enable)");
-  float* dst = net == 2 ? h->beta2 + agent * 4 : h->beta + agent * 8 + (net ? 4 : 0);
-  HIPCHK(h, hipMemcpyAsync(dst, in2, 8, hipMemcpyHostToDevice, h->stream));
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  return 0;
+  return write_beta_powers(h, net == 2 ? h->c2.beta + agent * 4 : h->beta + agent * 8 + (net ? 4 : 0), in2);
 }
 
 // ----------------------------------------------------------------- replay
@@ -2308,58 +2395,6 @@ int mdp_q_values(mdp_handle* h, int32_t agent, int32_t target, const float* x_de
 }
 
 // ---------------------------------------------------------------- training
-// MATD3's host counters: the launches about to be issued or captured count from
-// the committed state; commit_rounds after they (or a graph replay of them) went out
-static void td3_begin(mdp_handle* h) {
-  for (int i = 0; i < MDP_MAX_AGENTS; ++i) h->td3_work[i] = h->td3_count[i];
-}
-// the host-side counts of `rounds` whole rounds that went out: the approximators'
-// step counts (inferred policies) and MATD3's update counts; a plain handle has neither
-static void commit_rounds(mdp_handle* h, int rounds) {
-  if (h->approx && rounds > 0) {  // inferred policies: every observer's pairs stepped once per round
-    for (int i = 0; i < h->cfg.n_agents; ++i)
-      if (apx_agent(h, i)) h->apx_count[i] += rounds;
-    h->apx_pending = -1;
-  }
-  if (!h->td3) return;
-  for (int i = 0; i < h->cfg.n_agents; ++i) h->td3_count[i] += rounds;
-}
-// key of a TD3 graph: what is captured depends on which agents are due for an actor step
-static std::vector<int> td3_key(const mdp_handle* h, int kind, const std::vector<int>& ks) {
-  std::vector<int> key{kind};
-  for (int i = 0; i < h->cfg.n_agents; ++i) key.push_back((int)(h->td3_count[i] % h->td3_delay));
-  key.insert(key.end(), ks.begin(), ks.end());
-  return key;
-}
-// the graph of `body` under `key`, captured on first use (counting from the committed state)
-static int td3_graph(mdp_handle* h, const std::vector<int>& key, const std::function<int()>& body,
-                     hipGraphExec_t* out) {
-  auto it = h->td3_exec.find(key);
-  if (it != h->td3_exec.end()) {
-    *out = it->second;
-    return 0;
-  }
-  td3_begin(h);
-  HIPCHK(h, hipStreamBeginCapture(h->stream, hipStreamCaptureModeThreadLocal));
-  h->capturing = true;
-  const int rc = body();
-  h->capturing = false;
-  hipGraph_t g = nullptr;
-  const hipError_t e = hipStreamEndCapture(h->stream, &g);
-  if (rc) {
-    if (g) (void)hipGraphDestroy(g);
-    return rc;
-  }
-  if (e != hipSuccess) return fail(h, "hipStreamEndCapture", e);
-  hipGraphExec_t x = nullptr;
-  const hipError_t ei = hipGraphInstantiate(&x, g, nullptr, nullptr, 0);
-  (void)hipGraphDestroy(g);
-  if (ei != hipSuccess) return fail(h, "hipGraphInstantiate", ei);
-  h->td3_exec.emplace(key, x);
-  *out = x;
-  return 0;
-}
-
 int mdp_update_gate(mdp_handle* h, int64_t t) {
   MDP_NEED(h);
   if (h->len < (int64_t)h->cfg.batch_size * h->cfg.max_episode_len) return 1;  // maddpg.py:162-163
@@ -2546,31 +2581,11 @@ int mdp_update_round(mdp_handle* h) {
     if (!rc) commit_rounds(h, 1);
     return rc;
   }
-  if (h->td3) {
-    hipGraphExec_t x = nullptr;
-    const int rc = td3_graph(h, td3_key(h, 0, {}), [&] { return round_launches(h); }, &x);
-    if (rc) return rc;
-    HIPCHK(h, hipGraphLaunch(x, h->stream));
-    commit_rounds(h, 1);
-    return 0;
-  }
-  if (!h->round_exec) {
-    HIPCHK(h, hipStreamBeginCapture(h->stream, hipStreamCaptureModeThreadLocal));
-    h->capturing = true;
-    const int rc = round_launches(h);
-    h->capturing = false;
-    hipGraph_t g = nullptr;
-    const hipError_t e = hipStreamEndCapture(h->stream, &g);
-    if (rc) {
-      if (g) (void)hipGraphDestroy(g);
-      return rc;
-    }
-    if (e != hipSuccess) return fail(h, "hipStreamEndCapture", e);
-    h->round_graph = g;
-    HIPCHK(h, hipGraphInstantiate(&h->round_exec, g, nullptr, nullptr, 0));
-  }
-  HIPCHK(h, hipGraphLaunch(h->round_exec, h->stream));
-  commit_rounds(h, 1);  // (the approximators' step counts; MATD3 returned above)
+  hipGraphExec_t x = nullptr;
+  const int rc = captured_graph(h, graph_key(h, 0, {}), [&] { return round_launches(h); }, &x);
+  if (rc) return rc;
+  HIPCHK(h, hipGraphLaunch(x, h->stream));
+  commit_rounds(h, 1);
   return 0;
 }
 
@@ -2610,23 +2625,11 @@ int mdp_dp_init(mdp_handle* h, const uint8_t* id128, int32_t world, int32_t rank
   h->dp_world = world;
   const char* g = getenv("MDP_DP_GRAPHS");
   h->dp_graphs = g && g[0] == '1';
-  // drop graphs captured without the collectives
-  for (auto& kv : h->step_exec) (void)hipGraphExecDestroy(kv.second);
-  for (auto& kv : h->multi_exec) (void)hipGraphExecDestroy(kv.second);
-  h->step_exec.clear();
-  h->multi_exec.clear();
-  if (h->round_exec) {
-    (void)hipGraphExecDestroy(h->round_exec);
-    h->round_exec = nullptr;
-  }
-  if (h->round_graph) {
-    (void)hipGraphDestroy(h->round_graph);
-    h->round_graph = nullptr;
-  }
+  // drop graphs captured without the collectives (the launches after a join
+  // stay as they were: neither eager counter starts over)
+  destroy_graphs(h, false);
   return 0;
 }
-
-static void drop_graphs(mdp_handle* h);
 
 int mdp_dp_xgmi_open(mdp_handle* h, int32_t world, int32_t rank, uint8_t* handle_out) {
   if (unusable(h) || !handle_out) return -1;
@@ -2716,7 +2719,7 @@ int mdp_dp_xgmi_enable(mdp_handle* h) {
   HIPCHK(h, hipStreamSynchronize(h->stream));
   h->p2p = true;
   h->dp_world = h->x_world;
-  drop_graphs(h);  // graphs captured without the exchange
+  destroy_graphs(h, true);  // graphs captured without the exchange
   return 0;
 }
 
@@ -2726,7 +2729,7 @@ int mdp_dp_xgmi_close(mdp_handle* h) {
   if (h->stream) HIPCHK(h, hipStreamSynchronize(h->stream));
   xgmi_release(h);
   if (!h->comm) h->dp_world = 1;
-  drop_graphs(h);
+  destroy_graphs(h, true);
   return 0;
 }
 
@@ -2778,25 +2781,6 @@ int mdp_set_graphs(mdp_handle* h, int32_t on) {
   return 0;
 }
 
-static void drop_graphs(mdp_handle* h) {
-  for (auto& kv : h->step_exec) (void)hipGraphExecDestroy(kv.second);
-  for (auto& kv : h->multi_exec) (void)hipGraphExecDestroy(kv.second);
-  for (auto& kv : h->td3_exec) (void)hipGraphExecDestroy(kv.second);
-  h->step_exec.clear();
-  h->multi_exec.clear();
-  h->td3_exec.clear();
-  h->eager_steps = 0;
-  if (h->round_exec) {
-    (void)hipGraphExecDestroy(h->round_exec);
-    h->round_exec = nullptr;
-  }
-  if (h->round_graph) {
-    (void)hipGraphDestroy(h->round_graph);
-    h->round_graph = nullptr;
-  }
-  h->eager_rounds = 0;
-}
-
 int mdp_set_update_mode(mdp_handle* h, int32_t mode) {
   if (unusable(h)) return -1;
   if (mode != 0 && mode != 1) return fail(h, "update mode must be 0 (strict) or 1 (throughput)");
@@ -2814,7 +2798,7 @@ int mdp_set_update_mode(mdp_handle* h, int32_t mode) {
   }
   if (mode != h->update_mode) {
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    drop_graphs(h);
+    destroy_graphs(h, true);
     h->update_mode = mode;
   }
   return 0;
@@ -2892,7 +2876,7 @@ int mdp_reduce_grad(mdp_handle* h, int32_t agent, int32_t net) {
   if (h->approx)
     return fail(h, "mdp_reduce_grad: the phase entry points serve data parallelism; inferred policies (mdp_approx_enable) use "
                    "mdp_update");
-  return do_reduce(h, agent, net ? 1 : 0);
+  return launch_reduce(h, opt_own(h, agent, net ? 1 : 0));
 }
 
 int mdp_apply_grad(mdp_handle* h, int32_t agent, int32_t net, float scale) {
@@ -2902,7 +2886,7 @@ int mdp_apply_grad(mdp_handle* h, int32_t agent, int32_t net, float scale) {
   if (h->approx)
     return fail(h, "mdp_apply_grad: the phase entry points serve data parallelism; inferred policies (mdp_approx_enable) use "
                    "mdp_update");
-  return do_apply(h, agent, net ? 1 : 0, false, scale);
+  return launch_apply(h, opt_own(h, agent, net ? 1 : 0), scale);
 }
 
 int mdp_get_stats(mdp_handle* h, int32_t agent, double out6[6]) {
@@ -3120,7 +3104,7 @@ int mdp_evaluate_q(mdp_handle* h, int64_t first_episode, int32_t episodes, int32
   a.u_in = u_dev;
   a.ret = nullptr;
   a.bench = nullptr;
-  a.theta2 = h->td3 ? h->theta2 : nullptr;
+  a.theta2 = h->td3 ? h->c2.theta : nullptr;
   a.steps = steps;
   a.ncrit = C;
   a.qin = lds_eval_q_in(h->L.topo);
@@ -3351,67 +3335,11 @@ static int train_step_body(mdp_handle* h, int rounds) {
     if (!rc) commit_rounds(h, rounds);
     return rc;
   }
-  if (h->td3) {
-    hipGraphExec_t x = nullptr;
-    const int rc = td3_graph(h, td3_key(h, 1, {rounds}), [&] { return step_launches(h, rounds); }, &x);
-    if (rc) return rc;
-    HIPCHK(h, hipGraphLaunch(x, h->stream));
-    commit_rounds(h, rounds);
-    return 0;
-  }
-  auto it = h->step_exec.find(rounds);
-  if (it == h->step_exec.end()) {
-    HIPCHK(h, hipStreamBeginCapture(h->stream, hipStreamCaptureModeThreadLocal));
-    h->capturing = true;
-    const int rc = step_launches(h, rounds);
-    h->capturing = false;
-    hipGraph_t g = nullptr;
-    const hipError_t e = hipStreamEndCapture(h->stream, &g);
-    if (rc) {
-      if (g) (void)hipGraphDestroy(g);
-      return rc;
-    }
-    if (e != hipSuccess) return fail(h, "hipStreamEndCapture", e);
-    hipGraphExec_t x = nullptr;
-    const hipError_t ei = hipGraphInstantiate(&x, g, nullptr, nullptr, 0);
-    (void)hipGraphDestroy(g);
-    if (ei != hipSuccess) return fail(h, "hipGraphInstantiate", ei);
-    it = h->step_exec.emplace(rounds, x).first;
-  }
-  HIPCHK(h, hipGraphLaunch(it->second, h->stream));
-  commit_rounds(h, rounds);  // (the approximators' step counts; MATD3 returned above)
-  return 0;
-}
-
-// several consecutive training steps captured as ONE graph (keyed by their
-// round counts): the launches are exactly those of the steps one by one, but a
-// graph launch boundary costs ~6.7 us on the GPU clock against ~1.5-2 us for a
-// kernel boundary inside a graph (tools/step_boundary.py)
-static int multi_body(mdp_handle* h, const std::vector<int>& ks);
-static int multi_graph(mdp_handle* h, const std::vector<int>& ks, hipGraphExec_t* out) {
-  if (h->td3) return td3_graph(h, td3_key(h, 2, ks), [&] { return multi_body(h, ks); }, out);
-  auto it = h->multi_exec.find(ks);
-  if (it != h->multi_exec.end()) {
-    *out = it->second;
-    return 0;
-  }
-  HIPCHK(h, hipStreamBeginCapture(h->stream, hipStreamCaptureModeThreadLocal));
-  h->capturing = true;
-  const int rc = multi_body(h, ks);
-  h->capturing = false;
-  hipGraph_t g = nullptr;
-  const hipError_t e = hipStreamEndCapture(h->stream, &g);
-  if (rc) {
-    if (g) (void)hipGraphDestroy(g);
-    return rc;
-  }
-  if (e != hipSuccess) return fail(h, "hipStreamEndCapture", e);
   hipGraphExec_t x = nullptr;
-  const hipError_t ei = hipGraphInstantiate(&x, g, nullptr, nullptr, 0);
-  (void)hipGraphDestroy(g);
-  if (ei != hipSuccess) return fail(h, "hipGraphInstantiate", ei);
-  h->multi_exec.emplace(ks, x);
-  *out = x;
+  const int rc = captured_graph(h, graph_key(h, 1, {rounds}), [&] { return step_launches(h, rounds); }, &x);
+  if (rc) return rc;
+  HIPCHK(h, hipGraphLaunch(x, h->stream));
+  commit_rounds(h, rounds);
   return 0;
 }
 
@@ -3432,6 +3360,14 @@ static int multi_body(mdp_handle* h, const std::vector<int>& ks) {
     }
   }
   return rc;
+}
+
+// several consecutive training steps captured as ONE graph (keyed by their
+// round counts): the launches are exactly those of the steps one by one, but a
+// graph launch boundary costs ~6.7 us on the GPU clock against ~1.5-2 us for a
+// kernel boundary inside a graph (tools/step_boundary.py)
+static int multi_graph(mdp_handle* h, const std::vector<int>& ks, hipGraphExec_t* out) {
+  return captured_graph(h, graph_key(h, 2, ks), [&] { return multi_body(h, ks); }, out);
 }
 
 int mdp_train_steps(mdp_handle* h, int32_t n, const int32_t* rounds, int32_t launch) {
@@ -3574,7 +3510,7 @@ int mdp_check_finite(mdp_handle* h, int64_t* nonfinite) {
   const float* sets[4] = {h->theta, h->target, h->m, h->v};
   for (const float* p : sets) HIPCHK(h, mdp_launch_count_nonfinite(p, h->L.PT, &h->ctl->nonfinite, h->stream));
   if (h->td3) {  // the second critic's sets (actor spans of its regions stay zero)
-    const float* twin[4] = {h->theta2, h->target2, h->m2, h->v2};
+    const float* twin[4] = {h->c2.theta, h->c2.target, h->c2.m, h->c2.v};
     for (const float* p : twin) HIPCHK(h, mdp_launch_count_nonfinite(p, h->L.PT, &h->ctl->nonfinite, h->stream));
   }
   if (h->approx) {  // every observer's approximator sets (the spans without one stay zero)
@@ -3670,7 +3606,7 @@ int mdp_per_enable(mdp_handle* h, void* buf_dev, int64_t bytes, float alpha, flo
   HIPCHK(h, hipMemcpyAsync(h->per_st, st, sizeof(st), hipMemcpyHostToDevice, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
   h->per = true;
-  drop_graphs(h);  // graphs captured with the uniform draw
+  destroy_graphs(h, true);  // graphs captured with the uniform draw
   // every filled row starts at the new-row priority; the cursor at the ring's present state
   if (per_sync(h, 0, true)) {
     h->per = false;
@@ -3715,23 +3651,24 @@ int mdp_td3_enable(mdp_handle* h, void* buf_dev, int64_t bytes, int32_t policy_d
   }
   HIPCHK(h, hipMemcpyAsync(b + tl.beta, beta.data(), 4 * beta.size(), hipMemcpyHostToDevice, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
-  h->theta2 = (float*)(b + tl.theta);
-  h->target2 = (float*)(b + tl.target);
-  h->m2 = (float*)(b + tl.m);
-  h->v2 = (float*)(b + tl.v);
-  h->grad2 = (float*)(b + tl.grad);
-  h->slab2 = (float*)(b + tl.slab);
-  h->stat2 = (double*)(b + tl.stat);
-  h->beta2 = (float*)(b + tl.beta);
-  h->stats2 = (double*)(b + tl.stats);
-  h->ticket2 = (uint32_t*)(b + tl.ticket);
-  h->ra_ctr2 = (uint32_t*)(b + tl.ctr);
-  h->ra_part2 = (uint64_t*)(b + tl.part);
+  mdp_handle::Critic2& c = h->c2;
+  c.theta = (float*)(b + tl.theta);
+  c.target = (float*)(b + tl.target);
+  c.m = (float*)(b + tl.m);
+  c.v = (float*)(b + tl.v);
+  c.grad = (float*)(b + tl.grad);
+  c.slab = (float*)(b + tl.slab);
+  c.stat = (double*)(b + tl.stat);
+  c.beta = (float*)(b + tl.beta);
+  c.stats = (double*)(b + tl.stats);
+  c.ticket = (uint32_t*)(b + tl.ticket);
+  c.ctr = (uint32_t*)(b + tl.ctr);
+  c.part = (uint64_t*)(b + tl.part);
   h->td3_delay = policy_delay;
   for (int i = 0; i < MDP_MAX_AGENTS; ++i) h->td3_count[i] = h->td3_work[i] = 0;
   h->td3 = true;
   h->general_grads = true;  // MATD3 runs on the general kernels: no actor_pre / critic_pre, no index prefetch
-  drop_graphs(h);
+  destroy_graphs(h, true);
   return 0;
 }
 
@@ -3741,7 +3678,7 @@ int mdp_td3_info(mdp_handle* h, int32_t agent, double out4[4]) {
   if (!out4) return fail(h, "mdp_td3_info: out4 is null");
   double q1 = 0.0, q2 = 0.0;
   HIPCHK(h, hipMemcpyAsync(&q1, h->stats + agent * 8, 8, hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(h, hipMemcpyAsync(&q2, h->stats2 + agent * 8, 8, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipMemcpyAsync(&q2, h->c2.stats + agent * 8, 8, hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
   out4[0] = (double)h->td3_count[agent];
   out4[1] = (double)(h->td3_count[agent] / h->td3_delay);
@@ -3783,7 +3720,7 @@ int mdp_minimax_enable(mdp_handle* h, const float* eps_host) {
     for (int j = 0; j < MDP_MAX_AGENTS; ++j) h->mm_eps[i][j] = (i < n && j < n && i != j) ? eps_host[i * n + j] : 0.f;
   h->minimax = true;
   h->general_grads = true;  // M3DDPG runs on the general kernels: no actor_pre / critic_pre, no index prefetch
-  drop_graphs(h);
+  destroy_graphs(h, true);
   return 0;
 }
 
@@ -3806,7 +3743,7 @@ int mdp_minimax_debug_adv(mdp_handle* h, float* critic_adv_dev, float* actor_adv
   HIPCHK(h, hipStreamSynchronize(h->stream));
   h->mm_adv_c = critic_adv_dev;
   h->mm_adv_a = actor_adv_dev;
-  drop_graphs(h);  // the pointers are kernel arguments of the captured launches
+  destroy_graphs(h, true);  // the pointers are kernel arguments of the captured launches
   return 0;
 }
 
@@ -3854,21 +3791,22 @@ int mdp_approx_enable(mdp_handle* h, void* buf_dev, int64_t bytes, float lambda)
   }
   HIPCHK(h, hipMemcpyAsync(b + al.beta, beta.data(), 4 * beta.size(), hipMemcpyHostToDevice, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
-  h->apx_buf = b;
-  h->apx_region = al.region;
-  h->apx_obs_stride = al.obs_stride;
-  h->apx_slab = (float*)(b + al.slab);
-  h->apx_stat = (double*)(b + al.stat);
-  h->apx_beta = (float*)(b + al.beta);
-  h->apx_ticket = (uint32_t*)(b + al.ticket);
-  h->apx_ctr = (uint32_t*)(b + al.ctr);
-  h->apx_part = (uint64_t*)(b + al.part);
+  mdp_handle::Approx& x = h->apx;
+  x.buf = b;
+  x.region = al.region;
+  x.obs_stride = al.obs_stride;
+  x.slab = (float*)(b + al.slab);
+  x.stat = (double*)(b + al.stat);
+  x.beta = (float*)(b + al.beta);
+  x.ticket = (uint32_t*)(b + al.ticket);
+  x.ctr = (uint32_t*)(b + al.ctr);
+  x.part = (uint64_t*)(b + al.part);
   h->apx_lambda = lambda;
   for (int i = 0; i < MDP_MAX_AGENTS; ++i) h->apx_count[i] = 0;
   h->apx_pending = -1;
   h->approx = true;
   h->general_grads = true;  // runs on the general kernels: no actor_pre / critic_pre, no index prefetch
-  drop_graphs(h);
+  destroy_graphs(h, true);
   return 0;
 }
 
@@ -3893,12 +3831,7 @@ int mdp_approx_set_params(mdp_handle* h, int32_t observer, int32_t agent, int32_
   if (!src) return fail(h, "mdp_approx_set_params: src is null");
   if (n != net_floats(h, agent, 0)) return fail(h, "mdp_approx_set_params: n differs from the actor's parameter count");
   h->started = true;
-  const NDesc& d = net_of(h, agent, 0);
-  const std::vector<float> buf = scatter_net(h, agent, 0, src);
-  HIPCHK(h, hipMemcpyAsync(apx_base(h, observer, which) + d.off, buf.data(), 4 * buf.size(), hipMemcpyHostToDevice,
-                           h->stream));
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  return 0;
+  return write_net(h, apx_base(h, observer, which), agent, 0, src);
 }
 
 int mdp_approx_get_params(mdp_handle* h, int32_t observer, int32_t agent, int32_t which, float* dst, int64_t n) {
@@ -3906,42 +3839,25 @@ int mdp_approx_get_params(mdp_handle* h, int32_t observer, int32_t agent, int32_
   if (which < MDP_APX_NET || which > MDP_APX_GRAD) return fail(h, "mdp_approx_get_params: which must be in 0..4");
   if (!dst) return fail(h, "mdp_approx_get_params: dst is null");
   if (n != net_floats(h, agent, 0)) return fail(h, "mdp_approx_get_params: n differs from the actor's parameter count");
-  const NDesc& d = net_of(h, agent, 0);
   if (which == MDP_APX_GRAD && h->apx_pending == observer) {
-    // a gradient-only launch: its partials are reduced on demand (no optimizer state moves)
-    const int p = agent < observer ? agent : agent - 1;
-    if (apx_reduce(h, observer, agent, p, nullptr)) return -1;
+    // a gradient-only launch: its partials are reduced on demand (no beta powers: no optimizer state moves)
+    OptNet o = opt_approx(h, observer, agent, agent < observer ? agent : agent - 1);
+    o.beta = nullptr;
+    if (launch_reduce(h, o)) return -1;
   }
-  std::vector<float> buf(d.size);
-  HIPCHK(h, hipMemcpyAsync(buf.data(), apx_base(h, observer, which) + d.off, 4 * buf.size(), hipMemcpyDeviceToHost,
-                           h->stream));
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  int64_t s = 0;
-  for (int t = 0; t < 6; ++t) {
-    int rows, cols;
-    logical_shape(h, agent, 0, t, &rows, &cols);
-    for (int r = 0; r < rows; ++r, s += cols)
-      std::memcpy(dst + s, buf.data() + (d.t[t].off - d.off) + (int64_t)r * d.t[t].cols, 4 * (int64_t)cols);
-  }
-  return 0;
+  return read_net(h, apx_base(h, observer, which), agent, 0, dst);
 }
 
 int mdp_approx_get_beta_powers(mdp_handle* h, int32_t observer, int32_t agent, float out2[2]) {
   if (need_apx(h, observer, agent < 0 ? -2 : agent, "mdp_approx_get_beta_powers")) return -1;
   if (!out2) return fail(h, "mdp_approx_get_beta_powers: out2 is null");
-  const float* src = h->apx_beta + ((int64_t)observer * h->cfg.n_agents + agent) * 4;
-  HIPCHK(h, hipMemcpyAsync(out2, src, 8, hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  return 0;
+  return read_beta_powers(h, h->apx.beta + ((int64_t)observer * h->cfg.n_agents + agent) * 4, out2);
 }
 
 int mdp_approx_set_beta_powers(mdp_handle* h, int32_t observer, int32_t agent, const float in2[2]) {
   if (need_apx(h, observer, agent < 0 ? -2 : agent, "mdp_approx_set_beta_powers")) return -1;
   if (!in2) return fail(h, "mdp_approx_set_beta_powers: in2 is null");
-  float* dst = h->apx_beta + ((int64_t)observer * h->cfg.n_agents + agent) * 4;
-  HIPCHK(h, hipMemcpyAsync(dst, in2, 8, hipMemcpyHostToDevice, h->stream));
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  return 0;
+  return write_beta_powers(h, h->apx.beta + ((int64_t)observer * h->cfg.n_agents + agent) * 4, in2);
 }
 
 int mdp_approx_info(mdp_handle* h, int32_t observer, int32_t agent, double out4[4]) {
@@ -3949,7 +3865,7 @@ int mdp_approx_info(mdp_handle* h, int32_t observer, int32_t agent, double out4[
   if (!out4) return fail(h, "mdp_approx_info: out4 is null");
   const int64_t nwg = h->L.nwg;
   std::vector<double> st(8 * (size_t)nwg);
-  const double* src = h->apx_stat + ((int64_t)observer * h->cfg.n_agents + agent) * nwg * 8;
+  const double* src = h->apx.stat + ((int64_t)observer * h->cfg.n_agents + agent) * nwg * 8;
   HIPCHK(h, hipMemcpyAsync(st.data(), src, 8 * st.size(), hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
   double ce = 0.0, en = 0.0;

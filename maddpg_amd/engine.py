@@ -322,17 +322,21 @@ class Engine:
         flat = self._flat_params(agent, which, params)
         self._c("mdp_set_params", agent, _lib.WHICH[which], _lib.fptr(flat), flat.size)
 
-    def get_params(self, agent, which):
+    def _read_params(self, agent, which, name, *ids):
+        """the six tensors (logical shapes) that getter `name` writes as one flat array"""
         shapes = self._flat_shapes(agent, which)
         n = sum(r * c for r, c in shapes)
         flat = np.empty(n, np.float32)
-        self._c("mdp_get_params", agent, _lib.WHICH[which], _lib.fptr(flat), n)
+        self._c(name, *ids, _lib.fptr(flat), n)
         out, s = {}, 0
         for k, (r, c) in zip(TENSOR_NAMES, shapes):
             a = flat[s:s + r * c].reshape(r, c)
             out[k] = a[0].copy() if k.startswith("b") else a.copy()
             s += r * c
         return out
+
+    def get_params(self, agent, which):
+        return self._read_params(agent, which, "mdp_get_params", agent, _lib.WHICH[which])
 
     def get_beta_powers(self, agent, net):
         b = np.empty(2, np.float32)
@@ -642,16 +646,7 @@ class Engine:
         self._c("mdp_approx_set_params", observer, agent, _lib.APX_WHICH[which], _lib.fptr(flat), flat.size)
 
     def get_approx_params(self, observer, agent, which):
-        shapes = self._flat_shapes(agent, "actor")
-        n = sum(r * c for r, c in shapes)
-        flat = np.empty(n, np.float32)
-        self._c("mdp_approx_get_params", observer, agent, _lib.APX_WHICH[which], _lib.fptr(flat), n)
-        out, s = {}, 0
-        for k, (r, c) in zip(TENSOR_NAMES, shapes):
-            a = flat[s:s + r * c].reshape(r, c)
-            out[k] = a[0].copy() if k.startswith("b") else a.copy()
-            s += r * c
-        return out
+        return self._read_params(agent, "actor", "mdp_approx_get_params", observer, agent, _lib.APX_WHICH[which])
 
     def get_approx_beta_powers(self, observer, agent):
         b = np.empty(2, np.float32)

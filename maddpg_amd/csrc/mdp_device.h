@@ -12,11 +12,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "mdp_topo.h"
+#include "mdp_carve.h"  // MDP_R, MDP_NW and the other layout constants host and kernels share
 
 #define MDP_NT 256          // threads per workgroup (4 waves)
-#define MDP_NW 4            // waves per workgroup
-#define MDP_R 16            // batch rows per workgroup tile
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
@@ -238,9 +236,6 @@ __device__ __forceinline__ double block_sum_d(double v, double* scratch) {
   __syncthreads();
   return t;
 }
-
-// odd leading dimension so the 16 row-reads of one fragment land on distinct banks
-__host__ __device__ __forceinline__ int lds_ld(int cols) { return (cols | 1); }
 
 // ------------------------------------------------------ MFMA layer tiles
 // Y[16][N] = act(X[16][K] @ W[K][N] + b)   X,Y in LDS; W,b global row-major [K][N]
@@ -866,17 +861,20 @@ __device__ __forceinline__ void colsum16(const float* X, int ldx, int ncols, flo
   }
 }
 
-// Arena-relative LDS carving for the dynamic shared segment.
+// Arena-relative LDS carving for the dynamic shared segment.  A kernel expands
+// its buffer list (mdp_carve.h) over a carve named `cv`.
 struct LdsCarve {
   float* base;
   int off;
   __device__ LdsCarve(float* p) : base(p), off(0) {}
   __device__ float* take(int n) {
     float* p = base + off;
-    off += (n + 3) & ~3;
+    off += mdp_r4(n);
     return p;
   }
 };
+#define MDP_CARVE_DECL(type, name, count) type* name = reinterpret_cast<type*>(cv.take(count));
+#define MDP_CARVE_SET(type, name, count) name = reinterpret_cast<type*>(cv.take(count));
 
 // ------------------------------------------- register-resident layers (H = 64)
 // Used by the fast gradient kernels (mdp_grads_r.hip).  Every weight a wave
@@ -887,8 +885,7 @@ struct LdsCarve {
 // column 4r + t, so a lane's B fragments at one k-step are 4 consecutive
 // floats of a weight row (one 16-B load).  Contraction index k = 4s + kq.
 #define MDP_RH 64   // hidden width of the register-resident path
-#define MDP_RLH 68  // LDS row stride of forward activations (4r + kq: 64 distinct banks)
-#define MDP_RLD 65  // LDS row stride of backward deltas (r + 16 kq + s: 64 distinct banks)
+// (MDP_RLH / MDP_RLD, the LDS row strides of its activations and deltas: mdp_carve.h)
 
 __device__ __forceinline__ f32x4 ld4(const float* __restrict__ p) { return *reinterpret_cast<const f32x4*>(p); }
 

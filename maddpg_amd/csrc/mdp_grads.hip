@@ -476,19 +476,11 @@ __device__ __forceinline__ void critic_body(const A& a, const Topo& T, const int
   const int ldr = lds_ld(T.row_stride), ldc = lds_ld(T.cin_max), ldh = H + 1;
   const int S = MDP_R * ldh;  // one activation slot
   LdsCarve cv(lds);
-  float* rowbuf = cv.take(MDP_R * ldr);
-  float* xt = cv.take(MDP_R * ldc);
-  float* xl = cv.take(MDP_R * ldc);
-  float* hA = cv.take((G + 1) * S);
-  float* hB = cv.take((G + 1) * S);
-  float* lg = cv.take((G + 1) * MDP_R * 8);
-  float* dq = cv.take(MDP_R);
-  int* cnt = reinterpret_cast<int*>(cv.take(MDP_MAX_AGENTS + 4));  // layer-1 units done per net, then the
-                                                                    // work-queue counter (fwd_phase_l12)
+  MDP_CARVE_CRITIC(MDP_CARVE_DECL, ldr, ldc, S, G)
   float* ys = nullptr;  // TWIN: the rows' fp32 TD target, kept for critic 2's loss seed
-  if constexpr (TWIN) ys = cv.take(MDP_R);
+  if constexpr (TWIN) { MDP_CARVE_TWIN(MDP_CARVE_SET) }
   float* dxa = nullptr;  // MM: d q' / d (action columns) of the rows
-  if constexpr (MM) dxa = cv.take(MDP_R * MDP_ACT_DIM * T.n);
+  if constexpr (MM) { MDP_CARVE_MM(MDP_CARVE_SET, T.n) }
 
   const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63, nw = blockDim.x >> 6;
   const int r0 = blk * MDP_R;
@@ -878,22 +870,9 @@ __device__ __forceinline__ void actor_body(const AA& a, const Topo& T, const int
   const int ldr = lds_ld(T.row_stride), ldc = lds_ld(T.cin_max), ldh = H + 1;
   const int S = MDP_R * ldh;
   LdsCarve cv(lds);
-  float* rowbuf = cv.take(MDP_R * ldr);
-  float* x = cv.take(MDP_R * ldc);
-  float* h1a = cv.take(S);
-  float* h2a = cv.take(S);
-  float* h1c = cv.take(S);
-  float* h2c = cv.take(S);
-  float* d2 = cv.take(S);
-  float* d1 = cv.take(S);
-  float* lg = cv.take(MDP_R * 8);
-  float* av = cv.take(MDP_R * 8);
-  float* da = cv.take(MDP_R * 8);
-  float* dl = cv.take(MDP_R * 8);
-  float* qv = cv.take(MDP_R * 8);
-  float* w1ai = cv.take(MDP_ACT_DIM * H);  // the critic's layer-1 rows of the a_i input (for da)
+  MDP_CARVE_ACTOR(MDP_CARVE_DECL, ldr, ldc, S, H)
   float* dxa = nullptr;  // MM: d q / d (action columns) of the rows
-  if constexpr (MM) dxa = cv.take(MDP_R * MDP_ACT_DIM * T.n);
+  if constexpr (MM) { MDP_CARVE_MM(MDP_CARVE_SET, T.n) }
 
   const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63, nw = blockDim.x >> 6;
   const int r0 = blk * MDP_R;
@@ -1214,14 +1193,7 @@ __global__ __launch_bounds__(4 * H) void k_approx_grad(ApproxArgs a) {
   const NDesc& na = aj.actor;
   const int od = aj.obs_dim, ldo = lds_ld(od), ldh = H + 1, S = MDP_R * ldh;
   LdsCarve cv(lds);
-  float* xo = cv.take(MDP_R * ldo);
-  float* h1 = cv.take(S);
-  float* h2 = cv.take(S);
-  float* d2 = cv.take(S);
-  float* d1 = cv.take(S);
-  float* lg = cv.take(MDP_R * 8);
-  float* av = cv.take(MDP_R * 8);
-  float* dl = cv.take(MDP_R * 8);
+  MDP_CARVE_APPROX(MDP_CARVE_DECL, ldo, S)
   const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63, nw = blockDim.x >> 6;
   const int r0 = blk * MDP_R;
   const int nvalid = min(MDP_R, a.B - r0);
@@ -1329,192 +1301,59 @@ __global__ __launch_bounds__(MDP_GEN_THREADS) void k_grad_pair(GradPairArgs p) {
 
 // ---------------------------------------------------------------- launchers
 namespace {
-template <int H>
-hipError_t launch_critic(const CriticArgs& a, int lds, hipStream_t s) {
-  static bool attr = false;
-  if (!attr) {
-    (void)hipFuncSetAttribute((const void*)k_critic_grad<H>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                              MDP_LDS_BUDGET);
-    (void)hipGetLastError();
-    attr = true;
-  }
-  mdp_launch(k_critic_grad<H>, dim3((a.B + MDP_R - 1) / MDP_R), dim3(MDP_GEN_THREADS), lds, s, a);
-  return hipGetLastError();
-}
-template <int H>
-hipError_t launch_critic_per(const CriticArgsPer& a, int lds, hipStream_t s) {
-  static bool attr = false;
-  if (!attr) {
-    (void)hipFuncSetAttribute((const void*)k_critic_grad<H, true, CriticArgsPer>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                              MDP_LDS_BUDGET);
-    (void)hipGetLastError();
-    attr = true;
-  }
-  mdp_launch(k_critic_grad<H, true, CriticArgsPer>, dim3((a.B + MDP_R - 1) / MDP_R), dim3(MDP_GEN_THREADS), lds, s, a);
-  return hipGetLastError();
-}
-template <int H>
-hipError_t launch_critic_twin(const CriticArgsTwin& a, int lds, hipStream_t s) {
-  static bool attr = false;
-  if (!attr) {
-    (void)hipFuncSetAttribute((const void*)k_critic_grad<H, false, CriticArgsTwin, true>,
-                              hipFuncAttributeMaxDynamicSharedMemorySize, MDP_LDS_BUDGET);
-    (void)hipGetLastError();
-    attr = true;
-  }
-  mdp_launch(k_critic_grad<H, false, CriticArgsTwin, true>, dim3((a.B + MDP_R - 1) / MDP_R), dim3(MDP_GEN_THREADS), lds,
-             s, a);
-  return hipGetLastError();
-}
-template <int H>
-hipError_t launch_critic_mm(const CriticArgsMm& a, int lds, hipStream_t s) {
-  static bool attr = false;
-  if (!attr) {
-    (void)hipFuncSetAttribute((const void*)k_critic_grad<H, false, CriticArgsMm, false, true>,
-                              hipFuncAttributeMaxDynamicSharedMemorySize, MDP_LDS_BUDGET);
-    (void)hipGetLastError();
-    attr = true;
-  }
-  mdp_launch(k_critic_grad<H, false, CriticArgsMm, false, true>, dim3((a.B + MDP_R - 1) / MDP_R),
-             dim3(MDP_GEN_THREADS), lds, s, a);
-  return hipGetLastError();
-}
-template <int H>
-hipError_t launch_actor_mm(const ActorArgsMm& a, int lds, hipStream_t s) {
-  static bool attr = false;
-  if (!attr) {
-    (void)hipFuncSetAttribute((const void*)k_actor_grad<H, ActorArgsMm, true>,
-                              hipFuncAttributeMaxDynamicSharedMemorySize, MDP_LDS_BUDGET);
-    (void)hipGetLastError();
-    attr = true;
-  }
-  mdp_launch(k_actor_grad<H, ActorArgsMm, true>, dim3((a.B + MDP_R - 1) / MDP_R), dim3(MDP_GEN_THREADS), lds, s, a);
-  return hipGetLastError();
-}
-template <int H>
-hipError_t launch_critic_apx(const CriticArgsApx& a, int lds, hipStream_t s) {
-  static bool attr = false;
-  if (!attr) {
-    (void)hipFuncSetAttribute((const void*)k_critic_grad<H, false, CriticArgsApx, false, false, true>,
-                              hipFuncAttributeMaxDynamicSharedMemorySize, MDP_LDS_BUDGET);
-    (void)hipGetLastError();
-    attr = true;
-  }
-  mdp_launch(k_critic_grad<H, false, CriticArgsApx, false, false, true>, dim3((a.B + MDP_R - 1) / MDP_R),
-             dim3(MDP_GEN_THREADS), lds, s, a);
-  return hipGetLastError();
-}
-template <int H>
-hipError_t launch_approx(const ApproxArgs& a, int lds, hipStream_t s) {
-  static bool attr = false;
-  if (!attr) {
-    (void)hipFuncSetAttribute((const void*)k_approx_grad<H>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                              MDP_LDS_BUDGET);
-    (void)hipGetLastError();
-    attr = true;
-  }
-  mdp_launch(k_approx_grad<H>, dim3(a.m * a.nwg), dim3(4 * H), lds, s, a);
-  return hipGetLastError();
-}
-template <int H>
-hipError_t launch_actor(const ActorArgs& a, int lds, hipStream_t s) {
-  static bool attr = false;
-  if (!attr) {
-    (void)hipFuncSetAttribute((const void*)k_actor_grad<H>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                              MDP_LDS_BUDGET);
-    (void)hipGetLastError();
-    attr = true;
-  }
-  mdp_launch(k_actor_grad<H>, dim3((a.B + MDP_R - 1) / MDP_R), dim3(MDP_GEN_THREADS), lds, s, a);
-  return hipGetLastError();
+int row_tiles(int B) { return (B + MDP_R - 1) / MDP_R; }
+// one workgroup of MDP_GEN_THREADS per tile
+template <auto K, typename A>
+hipError_t launch_gen(int tiles, int lds, hipStream_t s, const A& a) {
+  return mdp_launch_lds<K>(dim3(tiles), dim3(MDP_GEN_THREADS), lds, s, a);
 }
 }  // namespace
 
-template <int H>
-hipError_t launch_pair(const GradPairArgs& a, int lds, hipStream_t s) {
-  static bool attr = false;
-  if (!attr) {
-    (void)hipFuncSetAttribute((const void*)k_grad_pair<H>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                              MDP_LDS_BUDGET);
-    (void)hipGetLastError();
-    attr = true;
-  }
-  mdp_launch(k_grad_pair<H>, dim3(2 * ((a.c.B + MDP_R - 1) / MDP_R)), dim3(MDP_GEN_THREADS), lds, s, a);
-  return hipGetLastError();
-}
-
 hipError_t mdp_launch_grad_pair(const GradPairArgs& a, int H, int lds_bytes, hipStream_t s) {
-  switch (H) {
-    case 64: return launch_pair<64>(a, lds_bytes, s);
-    case 128: return launch_pair<128>(a, lds_bytes, s);
-    case 256: return launch_pair<256>(a, lds_bytes, s);
-    default: return hipErrorInvalidValue;
-  }
+  return mdp_for_width(H, [&](auto h) {
+    return launch_gen<k_grad_pair<h.value>>(2 * row_tiles(a.c.B), lds_bytes, s, a);
+  });
 }
-
 hipError_t mdp_launch_critic_grad(const CriticArgs& a, int H, int lds_bytes, hipStream_t s) {
-  switch (H) {
-    case 64: return launch_critic<64>(a, lds_bytes, s);
-    case 128: return launch_critic<128>(a, lds_bytes, s);
-    case 256: return launch_critic<256>(a, lds_bytes, s);
-    default: return hipErrorInvalidValue;
-  }
+  return mdp_for_width(H, [&](auto h) {
+    return launch_gen<k_critic_grad<h.value>>(row_tiles(a.B), lds_bytes, s, a);
+  });
 }
 hipError_t mdp_launch_critic_grad_per(const CriticArgsPer& a, int H, int lds_bytes, hipStream_t s) {
-  switch (H) {
-    case 64: return launch_critic_per<64>(a, lds_bytes, s);
-    case 128: return launch_critic_per<128>(a, lds_bytes, s);
-    case 256: return launch_critic_per<256>(a, lds_bytes, s);
-    default: return hipErrorInvalidValue;
-  }
+  return mdp_for_width(H, [&](auto h) {
+    return launch_gen<k_critic_grad<h.value, true, CriticArgsPer>>(row_tiles(a.B), lds_bytes, s, a);
+  });
 }
 hipError_t mdp_launch_critic_grad_twin(const CriticArgsTwin& a, int H, int lds_bytes, hipStream_t s) {
-  switch (H) {
-    case 64: return launch_critic_twin<64>(a, lds_bytes, s);
-    case 128: return launch_critic_twin<128>(a, lds_bytes, s);
-    case 256: return launch_critic_twin<256>(a, lds_bytes, s);
-    default: return hipErrorInvalidValue;
-  }
+  return mdp_for_width(H, [&](auto h) {
+    return launch_gen<k_critic_grad<h.value, false, CriticArgsTwin, true>>(row_tiles(a.B), lds_bytes, s, a);
+  });
 }
 hipError_t mdp_launch_critic_grad_mm(const CriticArgsMm& a, int H, int lds_bytes, hipStream_t s) {
-  switch (H) {
-    case 64: return launch_critic_mm<64>(a, lds_bytes, s);
-    case 128: return launch_critic_mm<128>(a, lds_bytes, s);
-    case 256: return launch_critic_mm<256>(a, lds_bytes, s);
-    default: return hipErrorInvalidValue;
-  }
+  return mdp_for_width(H, [&](auto h) {
+    return launch_gen<k_critic_grad<h.value, false, CriticArgsMm, false, true>>(row_tiles(a.B), lds_bytes, s, a);
+  });
 }
 hipError_t mdp_launch_actor_grad_mm(const ActorArgsMm& a, int H, int lds_bytes, hipStream_t s) {
-  switch (H) {
-    case 64: return launch_actor_mm<64>(a, lds_bytes, s);
-    case 128: return launch_actor_mm<128>(a, lds_bytes, s);
-    case 256: return launch_actor_mm<256>(a, lds_bytes, s);
-    default: return hipErrorInvalidValue;
-  }
+  return mdp_for_width(H, [&](auto h) {
+    return launch_gen<k_actor_grad<h.value, ActorArgsMm, true>>(row_tiles(a.B), lds_bytes, s, a);
+  });
 }
 hipError_t mdp_launch_critic_grad_apx(const CriticArgsApx& a, int H, int lds_bytes, hipStream_t s) {
-  switch (H) {
-    case 64: return launch_critic_apx<64>(a, lds_bytes, s);
-    case 128: return launch_critic_apx<128>(a, lds_bytes, s);
-    case 256: return launch_critic_apx<256>(a, lds_bytes, s);
-    default: return hipErrorInvalidValue;
-  }
+  return mdp_for_width(H, [&](auto h) {
+    return launch_gen<k_critic_grad<h.value, false, CriticArgsApx, false, false, true>>(row_tiles(a.B), lds_bytes, s,
+                                                                                        a);
+  });
 }
 hipError_t mdp_launch_approx_grad(const ApproxArgs& a, int H, int lds_bytes, hipStream_t s) {
-  switch (H) {
-    case 64: return launch_approx<64>(a, lds_bytes, s);
-    case 128: return launch_approx<128>(a, lds_bytes, s);
-    case 256: return launch_approx<256>(a, lds_bytes, s);
-    default: return hipErrorInvalidValue;
-  }
+  return mdp_for_width(H, [&](auto h) {
+    return mdp_launch_lds<k_approx_grad<h.value>>(dim3(a.m * a.nwg), dim3(4 * h.value), lds_bytes, s, a);
+  });
 }
 hipError_t mdp_launch_actor_grad(const ActorArgs& a, int H, int lds_bytes, hipStream_t s) {
-  switch (H) {
-    case 64: return launch_actor<64>(a, lds_bytes, s);
-    case 128: return launch_actor<128>(a, lds_bytes, s);
-    case 256: return launch_actor<256>(a, lds_bytes, s);
-    default: return hipErrorInvalidValue;
-  }
+  return mdp_for_width(H, [&](auto h) {
+    return launch_gen<k_actor_grad<h.value>>(row_tiles(a.B), lds_bytes, s, a);
+  });
 }
 
 #ifdef MDP_STAMPS

@@ -338,11 +338,7 @@ __device__ __forceinline__ void actor_pre_tile(const CriticArgs& a, float* lds, 
   const ADesc& ag = T.ag[a.agent];
   const int ldr = lds_ld(T.row_stride);
   LdsCarve cv(lds);
-  float* rowbuf = cv.take(MDP_R * ldr);
-  float* h1a = cv.take(MDP_R * LH);
-  float* h2a = cv.take(MDP_R * LH);
-  float* lg = cv.take(MDP_R * 8);
-  float* av = cv.take(MDP_R * 8);
+  MDP_CARVE_ACTOR_PRE(MDP_CARVE_DECL, ldr)
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int r0 = bx * MDP_R, nvalid = min(MDP_R, a.B - r0);
   if (threadIdx.x == 0) *rows_ready = 0;
@@ -391,13 +387,7 @@ __device__ __forceinline__ void critic_pre_tile(const ActorArgs& a, float* lds, 
   const int kb = MDP_ACT_DIM * na, ldA = lds_ld(kb);
   const int ka_t = T.sum_obs, xo_t = T.ag[0].nobs_off, ka_c = ag.cin;
   LdsCarve cv(lds);
-  float* rowbuf = cv.take(MDP_R * ldr);
-  float* xa = cv.take(MDP_R * ldA);
-  float* lg = cv.take(3 * MDP_R * 8);
-  float* h1a = cv.take(3 * MDP_R * LH);
-  float* h2a = cv.take(3 * MDP_R * LH);
-  float* h1c = cv.take(MDP_R * LH);
-  float* h2c = cv.take(MDP_R * LH);
+  MDP_CARVE_CRITIC_PRE(MDP_CARVE_DECL, ldr, ldA)
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int lane = threadIdx.x & 63, r = lane & 15, kq = lane >> 4;
   const int r0 = bx * MDP_R, nvalid = min(MDP_R, a.B - r0);
@@ -590,20 +580,7 @@ __global__ __launch_bounds__(512) void k_critic_grad_r(A a) {
   const int xo_c = lq ? ag.obs_off : 0;
   const int kb_c = lq ? MDP_ACT_DIM : 0;
   LdsCarve cv(lds);
-  float* rowbuf = cv.take(MDP_R * ldr);
-  float* xa = cv.take(MDP_R * ldA);
-  float* lg = cv.take(3 * MDP_R * 8);
-  float* h1a = cv.take(3 * MDP_R * LH);
-  float* h2a = cv.take(3 * MDP_R * LH);
-  float* h1c = cv.take(MDP_R * LH);
-  float* h2c = cv.take(MDP_R * LH);
-  float* h1t = cv.take(MDP_R * LH);
-  float* h2t = cv.take(MDP_R * LH);
-  float* qv = cv.take(MDP_R);
-  float* qn = cv.take(MDP_R);
-  float* dq = cv.take(MDP_R);
-  float* d2 = cv.take(MDP_R * LD);
-  float* d1 = cv.take(MDP_R * LD);
+  MDP_CARVE_CRITIC_R(MDP_CARVE_DECL, ldr, ldA)
 
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int lane = threadIdx.x & 63, r = lane & 15, kq = lane >> 4;
@@ -1046,22 +1023,7 @@ __global__ __launch_bounds__(512) void k_actor_grad_r(ActorArgs a) {
   const int ka_c = lq ? ag.obs_dim : ag.cin;  // critic input from the replay row (a_i rows masked)
   const int xo_c = lq ? ag.obs_off : 0;
   LdsCarve cv(lds);
-  float* rowbuf = cv.take(MDP_R * ldr);
-  float* av = cv.take(MDP_R * 8);
-  float* lg = cv.take(MDP_R * 8);
-  float* da = cv.take(MDP_R * 8);
-  float* dl = cv.take(MDP_R * 8);
-  float* qv = cv.take(MDP_R);
-  float* h1a = cv.take(MDP_R * LH);
-  float* h2a = cv.take(MDP_R * LH);
-  float* h1c = cv.take(MDP_R * LH);
-  float* d2c = cv.take(MDP_R * LD);
-  float* d1c = cv.take(MDP_R * LD);
-  float* d2a = cv.take(MDP_R * LD);
-  float* d1a = cv.take(MDP_R * LD);
-  float* l1part = cv.take(2 * 64 * 16);  // critic L1 partial accumulators of waves 2, 3
-  float* gwpart = cv.take(4 * MDP_ACT_DIM * 64);  // dW3a partials of the four row quarters
-  float* qpart = cv.take(4 * MDP_R);     // critic head partials of the four L2 column tiles
+  MDP_CARVE_ACTOR_R(MDP_CARVE_DECL, ldr)
 
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int lane = threadIdx.x & 63, r = lane & 15, kq = lane >> 4;
@@ -1263,47 +1225,36 @@ __global__ __launch_bounds__(512) void k_actor_grad_r(ActorArgs a) {
 }
 
 namespace {
-template <typename K, typename A>
-hipError_t launch_r(K kern, const A& a, int lds, hipStream_t s, bool& attr, int extra = 0) {
-  if (!attr) {
-    (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, MDP_LDS_BUDGET);
-    (void)hipGetLastError();
-    attr = true;
-  }
-  const int per = (a.B + MDP_RW - 1) / MDP_RW;
-  mdp_launch(kern, dim3(per * (a.multi > 1 ? a.multi : 1) + extra), dim3(512), lds, s, a);
-  return hipGetLastError();
+int row_tiles(int B) { return (B + MDP_RW - 1) / MDP_RW; }
+// 512 threads per row tile of every agent in the launch, then `extra` workgroups of the other roles
+template <auto K, typename A>
+hipError_t launch_r(const A& a, int lds, hipStream_t s, int extra) {
+  return mdp_launch_lds<K>(dim3(row_tiles(a.B) * (a.multi > 1 ? a.multi : 1) + extra), dim3(512), lds, s, a);
 }
-}  // namespace
-
 // some agent of the topology narrower than MDP_ACT_DIM: the NARROW instantiations
-static bool topo_narrow(const Topo& t) {
+bool topo_narrow(const Topo& t) {
   for (int j = 0; j < t.n; ++j)
     if (topo_act_w(t, j) != MDP_ACT_DIM) return true;
   return false;
 }
+}  // namespace
 
 hipError_t mdp_launch_critic_grad_r(const CriticArgs& a, int lds_bytes, hipStream_t s) {
-  static bool attr = false, attr_n = false;
-  const int per = (a.B + MDP_RW - 1) / MDP_RW;
   // grid: critic row tiles | actor-forward row tiles (a.apre) | the index draw (pf_count; last)
-  const int extra = (a.apre ? per : 0) + (a.pf_count > 0 ? 1 : 0);
-  if (topo_narrow(a.topo)) return launch_r(k_critic_grad_r<false, true, CriticArgs>, a, lds_bytes, s, attr_n, extra);
-  return launch_r(k_critic_grad_r<false, false, CriticArgs>, a, lds_bytes, s, attr, extra);
+  const int extra = (a.apre ? row_tiles(a.B) : 0) + (a.pf_count > 0 ? 1 : 0);
+  if (topo_narrow(a.topo)) return launch_r<k_critic_grad_r<false, true, CriticArgs>>(a, lds_bytes, s, extra);
+  return launch_r<k_critic_grad_r<false, false, CriticArgs>>(a, lds_bytes, s, extra);
 }
 hipError_t mdp_launch_critic_grad_r_per(const CriticArgsPer& a, int lds_bytes, hipStream_t s) {
-  static bool attr = false, attr_n = false;
-  const int per = (a.B + MDP_RW - 1) / MDP_RW;
-  const int extra = (a.apre ? per : 0) + (a.pf_count > 0 ? 1 : 0);
-  if (topo_narrow(a.topo)) return launch_r(k_critic_grad_r<true, true, CriticArgsPer>, a, lds_bytes, s, attr_n, extra);
-  return launch_r(k_critic_grad_r<true, false, CriticArgsPer>, a, lds_bytes, s, attr, extra);
+  const int extra = (a.apre ? row_tiles(a.B) : 0) + (a.pf_count > 0 ? 1 : 0);
+  if (topo_narrow(a.topo)) return launch_r<k_critic_grad_r<true, true, CriticArgsPer>>(a, lds_bytes, s, extra);
+  return launch_r<k_critic_grad_r<true, false, CriticArgsPer>>(a, lds_bytes, s, extra);
 }
 hipError_t mdp_launch_actor_grad_r(const ActorArgs& a, int lds_bytes, hipStream_t s) {
-  static bool attr = false, attr_n = false;
   // grid: actor row tiles | the next critic step's row tiles (a.cpre)
-  const int extra = a.cpre ? (a.B + MDP_RW - 1) / MDP_RW : 0;
-  if (topo_narrow(a.topo)) return launch_r(k_actor_grad_r<true>, a, lds_bytes, s, attr_n, extra);
-  return launch_r(k_actor_grad_r<false>, a, lds_bytes, s, attr, extra);
+  const int extra = a.cpre ? row_tiles(a.B) : 0;
+  if (topo_narrow(a.topo)) return launch_r<k_actor_grad_r<true>>(a, lds_bytes, s, extra);
+  return launch_r<k_actor_grad_r<false>>(a, lds_bytes, s, extra);
 }
 
 #ifdef MDP_TIMELINE

@@ -1,9 +1,15 @@
-// mdp_kernels.h -- kernel argument blocks and host-side launchers.
+// mdp_kernels.h -- what the host needs to start the kernels: their argument
+// blocks, the dynamic-LDS size of every launch (summed from the kernels' own
+// buffer lists, mdp_carve.h), the launch helpers the kernel files share and the
+// mdp_launch_* entry points they define.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
 #include <stdint.h>
 
+#include <type_traits>
+
+#include "mdp_carve.h"
 #include "mdp_topo.h"
 
 // Argument blocks: the scalars and pointers a kernel reads first come first and
@@ -444,48 +450,70 @@ struct EvalArgs {
 // are instantiated for H = 64, 128, 256 (the fast register-resident ones for 64)
 inline int mdp_device_units(int u) { return u <= 64 ? 64 : (u <= 128 ? 128 : 256); }
 
-// ---- dynamic LDS sizes (must mirror the LdsCarve order in the kernels)
-inline int mdp_r4(int n) { return (n + 3) & ~3; }
-inline int mdp_ld(int c) { return c | 1; }
-// k_critic_grad / k_actor_grad (mdp_grads.hip); FJob/HJob are 48-byte LDS job records
+// ---- dynamic LDS sizes: each function sums the buffer list its kernel carves
+// (mdp_carve.h), with the list's parameters computed from the Topo
+// k_critic_grad / k_actor_grad (mdp_grads.hip)
 inline int lds_critic_bytes(const Topo& t, int G) {
-  const int R = 16, ldr = mdp_ld(t.row_stride), ldc = mdp_ld(t.cin_max), S = R * (t.H + 1);
-  return 4 * (mdp_r4(R * ldr) + 2 * mdp_r4(R * ldc) + 2 * mdp_r4((G + 1) * S) + mdp_r4((G + 1) * R * 8) +
-              mdp_r4(R) + mdp_r4(MDP_MAX_AGENTS + 4));
+  int words = 0;
+  MDP_CARVE_CRITIC(MDP_CARVE_WORDS, lds_ld(t.row_stride), lds_ld(t.cin_max), MDP_R * (t.H + 1), G)
+  return 4 * words;
 }
-// the twin instantiation keeps the rows' fp32 TD target for critic 2's loss seed
-inline int lds_critic_twin_bytes(const Topo& t, int G) { return lds_critic_bytes(t, G) + 4 * mdp_r4(16); }
+inline int lds_critic_twin_bytes(const Topo& t, int G) {
+  int words = 0;
+  MDP_CARVE_TWIN(MDP_CARVE_WORDS)
+  return lds_critic_bytes(t, G) + 4 * words;
+}
 inline int lds_actor_bytes(const Topo& t) {
-  const int R = 16, ldr = mdp_ld(t.row_stride), ldc = mdp_ld(t.cin_max), S = R * (t.H + 1);
-  return 4 * (mdp_r4(R * ldr) + mdp_r4(R * ldc) + 6 * mdp_r4(S) + 5 * mdp_r4(R * 8) + mdp_r4(5 * t.H));
+  int words = 0;
+  MDP_CARVE_ACTOR(MDP_CARVE_WORDS, lds_ld(t.row_stride), lds_ld(t.cin_max), MDP_R * (t.H + 1), t.H)
+  return 4 * words;
 }
-// the minimax instantiations keep the rows' gradient to every action column
-inline int lds_mm_dxa(const Topo& t) { return mdp_r4(16 * MDP_ACT_DIM * t.n); }
+// the minimax instantiations' tail, in words
+inline int lds_mm_dxa(const Topo& t) {
+  int words = 0;
+  MDP_CARVE_MM(MDP_CARVE_WORDS, t.n)
+  return words;
+}
 inline int lds_critic_mm_bytes(const Topo& t, int G) { return lds_critic_bytes(t, G) + 4 * lds_mm_dxa(t); }
 inline int lds_actor_mm_bytes(const Topo& t) { return lds_actor_bytes(t) + 4 * lds_mm_dxa(t); }
-// k_approx_grad: the rows' obs_j and act_j, four activation slots, logits and their seed
+// k_approx_grad, sized for the widest observation (a workgroup carves its own agent's)
 inline int mdp_approx_threads(int H) { return 4 * H; }  // one forward tile per wave
 inline int lds_approx_bytes(const Topo& t) {
   int omax = 1;
   for (int j = 0; j < t.n; ++j) omax = t.ag[j].obs_dim > omax ? t.ag[j].obs_dim : omax;
-  const int R = 16, S = R * (t.H + 1);
-  return 4 * (mdp_r4(R * mdp_ld(omax)) + 4 * mdp_r4(S) + 3 * mdp_r4(R * 8));
+  int words = 0;
+  MDP_CARVE_APPROX(MDP_CARVE_WORDS, lds_ld(omax), MDP_R * (t.H + 1))
+  return 4 * words;
 }
 #define MDP_LDS_BUDGET (160 * 1024)
 // fast (register-resident, H = 64) variants in mdp_grads_r.hip
+// actor_pre role of k_critic_grad_r (actor_pre_tile)
+inline int lds_actor_pre_bytes(const Topo& t) {
+  int words = 0;
+  MDP_CARVE_ACTOR_PRE(MDP_CARVE_WORDS, lds_ld(t.row_stride))
+  return 4 * words;
+}
+// k_critic_grad_r, whose launch also holds the actor_pre workgroups (the smaller carve)
 inline int lds_critic_r_bytes(const Topo& t, int agent) {
-  const int R = 16, ldr = mdp_ld(t.row_stride), LH = 68, LD = 65;
-  const int na = t.ag[agent].local_q ? 1 : t.n, ldA = mdp_ld(5 * na);
-  return 4 * (mdp_r4(R * ldr) + mdp_r4(R * ldA) + 3 * R * 8 + 6 * R * LH + 4 * R * LH + 3 * R + 2 * mdp_r4(R * LD));
+  const int na = t.ag[agent].local_q ? 1 : t.n;
+  int words = 0;
+  MDP_CARVE_CRITIC_R(MDP_CARVE_WORDS, lds_ld(t.row_stride), lds_ld(MDP_ACT_DIM * na))
+  const int pre = lds_actor_pre_bytes(t);
+  return 4 * words > pre ? 4 * words : pre;
 }
 inline int lds_actor_r_bytes(const Topo& t) {
-  const int R = 16, ldr = mdp_ld(t.row_stride), LH = 68, LD = 65;
-  return 4 * (mdp_r4(R * ldr) + 4 * R * 8 + R + 3 * R * LH + 4 * mdp_r4(R * LD) + 2 * 64 * 16 + 4 * R + 4 * 5 * 64);
+  int words = 0;
+  MDP_CARVE_ACTOR_R(MDP_CARVE_WORDS, lds_ld(t.row_stride))
+  return 4 * words;
 }
-// critic_pre role of k_actor_grad_r (mirrors critic_pre_tile's carve)
+// critic_pre role of k_actor_grad_r (critic_pre_tile, always a MADDPG critic's).
+// Exact: the hand-written formula this replaces counted 5632 bytes the tile
+// never takes; the launch uses max(lds_actor_r_bytes, this), which the actor
+// carve decides either way
 inline int lds_critic_pre_bytes(const Topo& t) {
-  const int R = 16, ldr = mdp_ld(t.row_stride), LH = 68, ldA = mdp_ld(5 * t.n);
-  return 4 * (mdp_r4(R * ldr) + mdp_r4(R * ldA) + 3 * R * 8 + 6 * R * LH + 3 * R * LH + 4 * R + 16 * R);
+  int words = 0;
+  MDP_CARVE_CRITIC_PRE(MDP_CARVE_WORDS, lds_ld(t.row_stride), lds_ld(MDP_ACT_DIM * t.n))
+  return 4 * words;
 }
 // the fast kernels hold every weight of a wave in registers: H = 64, at most 3
 // target actors, actor inputs <= 64, critic inputs <= 80, target-critic action part <= 20
@@ -500,16 +528,19 @@ inline bool grads_r_ok(const Topo& t, int agent) {
   if ((ag.local_q ? ag.obs_dim : t.sum_obs) > 64) return false;
   return 5 * na <= 20;
 }
+// k_rollout, k_eval_episodes
 inline int lds_rollout_bytes(const Topo& t) {
-  const int R = 16, ldr = mdp_ld(t.row_stride), ldh = t.H + 1;
-  const int par = t.H == 64 ? 4 * (2 * R * 68 + R * 8) : 0;  // k_rollout's per-agent forward slots (H = 64)
-  return 4 * (mdp_r4(R * ldr) + 2 * mdp_r4(R * ldh) + mdp_r4(R * 8) + par + 2 * mdp_r4(R * 2 * MDP_MAX_ENT) +
-              mdp_r4(R * 3 * MDP_MAX_ENT) + mdp_r4(R * MDP_MAX_AGENTS) + mdp_r4(R));
+  int words = 0;
+  MDP_CARVE_ROLLOUT(MDP_CARVE_WORDS, lds_ld(t.row_stride), t.H + 1, MDP_ROLLOUT_PAR_W(t.H))
+  return 4 * words;
 }
-// k_eval_episodes<H, EvalMuArgs>: k_rollout's carve plus the matchup's table row
-inline int lds_eval_matchups_bytes(const Topo& t) { return lds_rollout_bytes(t) + 4 * mdp_r4(MDP_MAX_AGENTS); }
-// k_eval_episodes<H, EvalQArgs>: k_rollout's carve plus the [obs_j | act_j] staging
-// tile of the local_q agents' critics (qin: the widest such input, 0 when none)
+// k_eval_episodes<H, EvalMuArgs>
+inline int lds_eval_matchups_bytes(const Topo& t) {
+  int words = 0;
+  MDP_CARVE_EVAL_MU(MDP_CARVE_WORDS)
+  return lds_rollout_bytes(t) + 4 * words;
+}
+// k_eval_episodes<H, EvalQArgs>; qin: the widest critic input of a local_q agent, 0 when none
 inline int lds_eval_q_in(const Topo& t) {
   int qin = 0;
   for (int j = 0; j < t.n; ++j)
@@ -518,11 +549,15 @@ inline int lds_eval_q_in(const Topo& t) {
 }
 inline int lds_eval_q_bytes(const Topo& t) {
   const int qin = lds_eval_q_in(t);
-  return lds_rollout_bytes(t) + (qin ? 4 * mdp_r4(16 * mdp_ld(qin)) : 0);
+  int words = 0;
+  if (qin) { MDP_CARVE_EVAL_QV(MDP_CARVE_WORDS, lds_ld(qin)) }
+  return lds_rollout_bytes(t) + 4 * words;
 }
+// k_mlp_eval
 inline int lds_eval_bytes(int in, int H) {
-  const int R = 16, ldx = mdp_ld(in), ldh = H + 1;
-  return 4 * (mdp_r4(R * ldx) + 2 * mdp_r4(R * ldh) + mdp_r4(R * 8));
+  int words = 0;
+  MDP_CARVE_MLP_EVAL(MDP_CARVE_WORDS, lds_ld(in), H + 1)
+  return 4 * words;
 }
 
 // ---- per-launch timing (bench.py's kernel pass): when the host armed a
@@ -544,6 +579,34 @@ inline void mdp_launch(F kernel, const dim3& grid, const dim3& block, uint32_t l
   } else {
     hipLaunchKernelGGL(kernel, grid, block, lds, s, args...);
   }
+}
+// the kernels' hidden widths: f(std::integral_constant<int, H>) for the H given
+template <typename F>
+inline hipError_t mdp_for_width(int H, F&& f) {
+  switch (H) {
+    case 64: return f(std::integral_constant<int, 64>{});
+    case 128: return f(std::integral_constant<int, 128>{});
+    case 256: return f(std::integral_constant<int, 256>{});
+    default: return hipErrorInvalidValue;
+  }
+}
+// before kernel instantiation K's first launch: let it take up to LIMIT bytes of
+// dynamic LDS (an unsupported opt-in must not poison the next launch check)
+template <auto K, int LIMIT>
+inline void mdp_raise_lds_limit() {
+  static bool done = false;
+  if (!done) {
+    (void)hipFuncSetAttribute((const void*)K, hipFuncAttributeMaxDynamicSharedMemorySize, LIMIT);
+    (void)hipGetLastError();
+    done = true;
+  }
+}
+// one launch of K with `lds` bytes of dynamic LDS, on the timed dispatch packet when one is armed
+template <auto K, int LIMIT = MDP_LDS_BUDGET, typename A>
+inline hipError_t mdp_launch_lds(const dim3& grid, const dim3& block, int lds, hipStream_t s, const A& a) {
+  mdp_raise_lds_limit<K, LIMIT>();
+  mdp_launch(K, grid, block, lds, s, a);
+  return hipGetLastError();
 }
 
 hipError_t mdp_launch_critic_grad(const CriticArgs& a, int H, int lds_bytes, hipStream_t s);

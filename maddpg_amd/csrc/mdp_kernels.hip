@@ -817,19 +817,10 @@ __global__ __launch_bounds__(MDP_NT) void k_rollout(RolloutArgs a) {
   const EnvDesc& E = a.env;
   const int n = E.n_agents, ne = E.n_agents + E.n_landmarks;
   const int ldr = lds_ld(T.row_stride), ldh = H + 1;
-  LdsCarve cv(lds);
-  float* rowt = cv.take(MDP_R * ldr);
-  float* h1 = cv.take(MDP_R * ldh);
-  float* h2 = cv.take(MDP_R * ldh);
-  float* lg = cv.take(MDP_R * 8);
   // H = 64: every agent's policy forward on its own wave (rollout_par), h1 | h2 | logits per agent
-  constexpr int PAR_W = H == 64 ? MDP_NW * (2 * MDP_R * MDP_RLH + MDP_R * 8) : 0;
-  float* hpar = cv.take(PAR_W);
-  float* sp = cv.take(MDP_R * 2 * MDP_MAX_ENT);
-  float* sv = cv.take(MDP_R * 2 * MDP_MAX_ENT);
-  float* sfo = cv.take(MDP_R * 3 * MDP_MAX_ENT);  // per-env force scratch of env_physics
-  float* epr = cv.take(MDP_R * MDP_MAX_AGENTS);    // the envs' running episode rewards
-  int* sgoal = reinterpret_cast<int*>(cv.take(MDP_R));  // the envs' goal landmarks
+  constexpr int PAR_W = MDP_ROLLOUT_PAR_W(H);
+  LdsCarve cv(lds);
+  MDP_CARVE_ROLLOUT(MDP_CARVE_DECL, ldr, ldh, PAR_W)
 
   const int tid = threadIdx.x;
   // with a draw workgroup it is block 0 (dispatched first: at tag6 B=4096 the
@@ -1155,26 +1146,17 @@ __global__ __launch_bounds__(MDP_NT) void k_eval_episodes(Args a) {
   const EnvDesc& E = a.env;
   const int n = E.n_agents;
   const int ldr = lds_ld(T.row_stride), ldh = H + 1;
-  LdsCarve cv(lds);  // k_rollout's carve (lds_rollout_bytes)
-  float* rowt = cv.take(MDP_R * ldr);
-  float* h1 = cv.take(MDP_R * ldh);
-  float* h2 = cv.take(MDP_R * ldh);
-  float* lg = cv.take(MDP_R * 8);
-  constexpr int PAR_W = H == 64 ? MDP_NW * (2 * MDP_R * MDP_RLH + MDP_R * 8) : 0;
-  float* hpar = cv.take(PAR_W);
-  float* sp = cv.take(MDP_R * 2 * MDP_MAX_ENT);
-  float* sv = cv.take(MDP_R * 2 * MDP_MAX_ENT);
-  float* sfo = cv.take(MDP_R * 3 * MDP_MAX_ENT);
-  float* epr = cv.take(MDP_R * MDP_MAX_AGENTS);  // the episodes' returns so far
-  int* sgoal = reinterpret_cast<int*>(cv.take(MDP_R));
-  // MU: the matchup's table row (lds_eval_matchups_bytes adds it behind k_rollout's carve)
-  int* stab = MU ? reinterpret_cast<int*>(cv.take(MDP_MAX_AGENTS)) : nullptr;
-  // QV: the local_q critics' input tile (lds_eval_q_bytes adds it behind k_rollout's carve)
+  constexpr int PAR_W = MDP_ROLLOUT_PAR_W(H);
+  LdsCarve cv(lds);
+  MDP_CARVE_ROLLOUT(MDP_CARVE_DECL, ldr, ldh, PAR_W)
+  int* stab = nullptr;  // MU: the matchup's table row
+  if constexpr (MU) { MDP_CARVE_EVAL_MU(MDP_CARVE_SET) }
+  // QV: the local_q critics' input tile
   int ldq = 0;
   float* qx = nullptr;
   if constexpr (QV) {
     ldq = lds_ld(a.qin);
-    qx = a.qin ? cv.take(MDP_R * ldq) : nullptr;
+    if (a.qin) { MDP_CARVE_EVAL_QV(MDP_CARVE_SET, ldq) }
   }
   // this step's records of the tile, [R][n][MDP_BENCH_W]: in h1, which is free
   // between a step's forward and the next one's
@@ -1443,10 +1425,7 @@ __global__ __launch_bounds__(MDP_NT) void k_mlp_eval(EvalArgs a) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const int ldx = lds_ld(a.in), ldh = H + 1;
   LdsCarve cv(lds);
-  float* x = cv.take(MDP_R * ldx);
-  float* h1 = cv.take(MDP_R * ldh);
-  float* h2 = cv.take(MDP_R * ldh);
-  float* lg = cv.take(MDP_R * 8);
+  MDP_CARVE_MLP_EVAL(MDP_CARVE_DECL, ldx, ldh)
   const int r0 = blockIdx.x * MDP_R;
   const int nvalid = min(MDP_R, a.rows - r0);
   for (int q = threadIdx.x; q < MDP_R * a.in; q += MDP_NT) {
@@ -1480,111 +1459,55 @@ __global__ __launch_bounds__(MDP_NT) void k_mlp_eval(EvalArgs a) {
     if (e_ != hipSuccess) return e_;   \
   } while (0)
 
-template <int H>
-static hipError_t launch_rollout_t(const RolloutArgs& a, int lds_bytes, hipStream_t s) {
-  const int grid = (a.E + MDP_R - 1) / MDP_R + (a.pf_count > 0 ? 1 : 0);
-  if (a.nsteps > 1)
-    mdp_launch(k_rollout<H, true>, dim3(grid), dim3(MDP_NT), lds_bytes, s, a);
-  else
-    mdp_launch(k_rollout<H, false>, dim3(grid), dim3(MDP_NT), lds_bytes, s, a);
-  MDP_CHECK_LAUNCH();
-  return hipSuccess;
-}
-template <int H>
-static hipError_t launch_eval_t(const EvalArgs& a, int lds_bytes, hipStream_t s) {
-  const int grid = (a.rows + MDP_R - 1) / MDP_R;
-  hipLaunchKernelGGL(k_mlp_eval<H>, dim3(grid), dim3(MDP_NT), lds_bytes, s, a);
-  MDP_CHECK_LAUNCH();
-  return hipSuccess;
-}
-
-static int set_lds_limit_done = 0;
-template <int H>
-static void raise_lds_limits() {
-  (void)hipFuncSetAttribute((const void*)k_rollout<H, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
-  (void)hipFuncSetAttribute((const void*)k_rollout<H, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
-  (void)hipFuncSetAttribute((const void*)k_mlp_eval<H>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
-  (void)hipFuncSetAttribute((const void*)k_eval_episodes<H>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
-  (void)hipFuncSetAttribute((const void*)k_eval_episodes<H, EvalMuArgs>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            128 * 1024);
-  (void)hipFuncSetAttribute((const void*)k_eval_episodes<H, EvalQArgs>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            128 * 1024);
-}
-static void ensure_lds_limits() {
-  if (!set_lds_limit_done) {
-    raise_lds_limits<64>();
-    raise_lds_limits<128>();
-    raise_lds_limits<256>();
-    (void)hipGetLastError();  // an unsupported opt-in must not poison the next launch check
-    set_lds_limit_done = 1;
-  }
+// the rollout / eval family: one workgroup of MDP_NT threads per 16 rows, up to 128 KB of dynamic LDS
+#define MDP_ENV_LDS_LIMIT (128 * 1024)
+// instantiated here, width by width: the order in which the kernels lie in the code object
+#define MDP_ENV_KERNELS(H)                                             \
+  template __global__ void k_rollout<H, false>(RolloutArgs);           \
+  template __global__ void k_rollout<H, true>(RolloutArgs);            \
+  template __global__ void k_mlp_eval<H>(EvalArgs);                    \
+  template __global__ void k_eval_episodes<H, EvalEpArgs>(EvalEpArgs); \
+  template __global__ void k_eval_episodes<H, EvalMuArgs>(EvalMuArgs); \
+  template __global__ void k_eval_episodes<H, EvalQArgs>(EvalQArgs);
+MDP_ENV_KERNELS(64)
+MDP_ENV_KERNELS(128)
+MDP_ENV_KERNELS(256)
+static int row_tiles(int rows) { return (rows + MDP_R - 1) / MDP_R; }
+template <auto K, typename A>
+static hipError_t launch_env(const dim3& grid, int lds, hipStream_t s, const A& a) {
+  return mdp_launch_lds<K, MDP_ENV_LDS_LIMIT>(grid, dim3(MDP_NT), lds, s, a);
 }
 
 hipError_t mdp_launch_rollout(const RolloutArgs& a, int H, int lds_bytes, hipStream_t s) {
-  ensure_lds_limits();
-  switch (H) {
-    case 64: return launch_rollout_t<64>(a, lds_bytes, s);
-    case 128: return launch_rollout_t<128>(a, lds_bytes, s);
-    case 256: return launch_rollout_t<256>(a, lds_bytes, s);
-    default: return hipErrorInvalidValue;
-  }
+  const dim3 grid(row_tiles(a.E) + (a.pf_count > 0 ? 1 : 0));
+  return mdp_for_width(H, [&](auto h) {
+    if (a.nsteps > 1) return launch_env<k_rollout<h.value, true>>(grid, lds_bytes, s, a);
+    return launch_env<k_rollout<h.value, false>>(grid, lds_bytes, s, a);
+  });
 }
 hipError_t mdp_launch_eval(const EvalArgs& a, int H, int lds_bytes, hipStream_t s) {
-  ensure_lds_limits();
-  switch (H) {
-    case 64: return launch_eval_t<64>(a, lds_bytes, s);
-    case 128: return launch_eval_t<128>(a, lds_bytes, s);
-    case 256: return launch_eval_t<256>(a, lds_bytes, s);
-    default: return hipErrorInvalidValue;
-  }
-}
-template <int H>
-static hipError_t launch_eval_episodes_t(const EvalEpArgs& a, int lds_bytes, hipStream_t s) {
-  mdp_launch(k_eval_episodes<H>, dim3((a.episodes + MDP_R - 1) / MDP_R), dim3(MDP_NT), lds_bytes, s, a);
-  MDP_CHECK_LAUNCH();
-  return hipSuccess;
+  return mdp_for_width(H, [&](auto h) {  // (never timed: a plain launch)
+    mdp_raise_lds_limit<k_mlp_eval<h.value>, MDP_ENV_LDS_LIMIT>();
+    hipLaunchKernelGGL(k_mlp_eval<h.value>, dim3(row_tiles(a.rows)), dim3(MDP_NT), lds_bytes, s, a);
+    return hipGetLastError();
+  });
 }
 hipError_t mdp_launch_eval_episodes(const EvalEpArgs& a, int H, int lds_bytes, hipStream_t s) {
-  ensure_lds_limits();
-  switch (H) {
-    case 64: return launch_eval_episodes_t<64>(a, lds_bytes, s);
-    case 128: return launch_eval_episodes_t<128>(a, lds_bytes, s);
-    case 256: return launch_eval_episodes_t<256>(a, lds_bytes, s);
-    default: return hipErrorInvalidValue;
-  }
+  return mdp_for_width(H, [&](auto h) {
+    return launch_env<k_eval_episodes<h.value>>(dim3(row_tiles(a.episodes)), lds_bytes, s, a);
+  });
 }
 // grid: tile fastest, matchup second -- the workgroups of one matchup are
 // adjacent and share its weights in L2
-template <int H>
-static hipError_t launch_eval_matchups_t(const EvalMuArgs& a, int lds_bytes, hipStream_t s) {
-  const dim3 grid((a.episodes + MDP_R - 1) / MDP_R, a.matchups);
-  mdp_launch(k_eval_episodes<H, EvalMuArgs>, grid, dim3(MDP_NT), lds_bytes, s, a);
-  MDP_CHECK_LAUNCH();
-  return hipSuccess;
-}
 hipError_t mdp_launch_eval_matchups(const EvalMuArgs& a, int H, int lds_bytes, hipStream_t s) {
-  ensure_lds_limits();
-  switch (H) {
-    case 64: return launch_eval_matchups_t<64>(a, lds_bytes, s);
-    case 128: return launch_eval_matchups_t<128>(a, lds_bytes, s);
-    case 256: return launch_eval_matchups_t<256>(a, lds_bytes, s);
-    default: return hipErrorInvalidValue;
-  }
-}
-template <int H>
-static hipError_t launch_eval_q_t(const EvalQArgs& a, int lds_bytes, hipStream_t s) {
-  mdp_launch(k_eval_episodes<H, EvalQArgs>, dim3((a.episodes + MDP_R - 1) / MDP_R), dim3(MDP_NT), lds_bytes, s, a);
-  MDP_CHECK_LAUNCH();
-  return hipSuccess;
+  return mdp_for_width(H, [&](auto h) {
+    return launch_env<k_eval_episodes<h.value, EvalMuArgs>>(dim3(row_tiles(a.episodes), a.matchups), lds_bytes, s, a);
+  });
 }
 hipError_t mdp_launch_eval_q(const EvalQArgs& a, int H, int lds_bytes, hipStream_t s) {
-  ensure_lds_limits();
-  switch (H) {
-    case 64: return launch_eval_q_t<64>(a, lds_bytes, s);
-    case 128: return launch_eval_q_t<128>(a, lds_bytes, s);
-    case 256: return launch_eval_q_t<256>(a, lds_bytes, s);
-    default: return hipErrorInvalidValue;
-  }
+  return mdp_for_width(H, [&](auto h) {
+    return launch_env<k_eval_episodes<h.value, EvalQArgs>>(dim3(row_tiles(a.episodes)), lds_bytes, s, a);
+  });
 }
 hipError_t mdp_launch_eval_returns(const EvalRetArgs& a, hipStream_t s) {
   const int64_t total = (int64_t)a.episodes * a.n;

@@ -334,6 +334,9 @@ struct mdp_handle {
   bool general_grads = false;
   // single-GPU optimizer step as one k_reduce_apply launch (MDP_UNFUSED_APPLY=1: k_reduce + k_apply)
   bool fused_apply = true;
+  // ... with the reduced gradient kept in registers where mdp_ra_lanes allows
+  // (MDP_RA_LANES=0: the LDS body for every launch -- tests and A/B runs)
+  bool ra_lanes = true;
   uint32_t* ra_ctr = nullptr;
   uint64_t* ra_part = nullptr;
   // the actor forward + sample of agent i computed by extra workgroups of its
@@ -1194,7 +1197,7 @@ int opt_step(mdp_handle* h, const OptNet& o, bool fused, float scale, int32_t* p
     }
     if (h->p2p && o.own) set_xchg(h, f);
     ProfScope p(h, MDP_K_REDUCE_APPLY);
-    HIPCHK(h, mdp_launch_reduce_apply(f, h->stream));
+    HIPCHK(h, mdp_launch_reduce_apply(f, h->stream, h->ra_lanes));
     return 0;
   }
   const int rc = launch_reduce(h, o);
@@ -1477,6 +1480,7 @@ int tp_setup(mdp_handle* h) {
     RaBatch& rb = *rbs[ph];
     rb.count = 2 * n;
     rb.narrow = h->L.nwg <= 64 ? 1 : 0;
+    bool lanes = h->ra_lanes && ph == 0;  // the register body: every net of the batch must allow it
     rb.wg_start[0] = 0;
     for (int i = 0; i < n; ++i)
       for (int net = 1; net >= 0; --net) {
@@ -1488,9 +1492,11 @@ int tp_setup(mdp_handle* h) {
           else f.phase = 0;  // unused list
         }
         list.push_back(f);
+        lanes = lanes && mdp_ra_lanes(f);
         const int q = 2 * i + (1 - net);
         rb.wg_start[q + 1] = rb.wg_start[q] + mdp_ra_grid(f);
       }
+    if (lanes) rb.narrow = 2;
   }
   for (int ph = 0; ph < 4; ++ph) {
     h->tp_host[ph].assign(list.begin() + 2 * n * ph, list.begin() + 2 * n * (ph + 1));
@@ -1508,6 +1514,7 @@ int tp_setup(mdp_handle* h) {
       rb = RaBatch();
       rb.count = 2;
       rb.narrow = h->L.nwg <= 64 ? 1 : 0;
+      bool lanes = h->ra_lanes && pp == 0;
       for (int k = 0; k < 2; ++k) {
         const int net = 1 - k;  // critic, then actor
         FusedApplyArgs f = tp_args(h, i, net);
@@ -1521,8 +1528,10 @@ int tp_setup(mdp_handle* h) {
         }
         list.push_back(f);
         h->tp_pair_host[pp][i][k] = f;
+        lanes = lanes && mdp_ra_lanes(f);
         rb.wg_start[k + 1] = rb.wg_start[k] + mdp_ra_grid(f);
       }
+      if (lanes) rb.narrow = 2;
       // + the draw workgroup; a reduce-only pass never spins
       h->tp_pair_fits[pp][i] = pp == 1 || rb.wg_start[2] + 1 <= h->ra_batch_cap;
     }
@@ -1635,7 +1644,7 @@ int launch_tp_pair(mdp_handle* h, int pp, int i, int32_t* piece) {
       f.pf_ctl = h->ctl;
     }
     ProfScope p(h, kind);
-    HIPCHK(h, mdp_launch_reduce_apply(f, h->stream));
+    HIPCHK(h, mdp_launch_reduce_apply(f, h->stream, h->ra_lanes));
   }
   return 0;
 }
@@ -1695,7 +1704,7 @@ int launch_tp_batch(mdp_handle* h, int ph) {
     HIPCHK(h, mdp_launch_reduce_apply_batch(*rbs[ph], h->stream));
     return 0;
   }
-  for (const FusedApplyArgs& f : h->tp_host[ph]) HIPCHK(h, mdp_launch_reduce_apply(f, h->stream));
+  for (const FusedApplyArgs& f : h->tp_host[ph]) HIPCHK(h, mdp_launch_reduce_apply(f, h->stream, h->ra_lanes));
   return 0;
 }
 
@@ -1989,6 +1998,8 @@ int mdp_create(const mdp_config* cfg, void* arena_dev, int64_t arena_bytes, void
     h->general_grads = g && g[0] == '1';
     const char* u = getenv("MDP_UNFUSED_APPLY");
     h->fused_apply = !(u && u[0] == '1');
+    const char* rl = getenv("MDP_RA_LANES");
+    h->ra_lanes = !(rl && rl[0] == '0');
     const char* rd = getenv("MDP_ROLLOUT_DRAW");
     h->rollout_draw = !(rd && rd[0] == '0');
     const char* da = getenv("MDP_DRAW_AHEAD");

@@ -8,6 +8,8 @@
 // Workgroup (tensor t, chunk c) of 256 parameters, 1024 threads: 16 groups of
 // 64 threads each sum a quarter-ish of the per-workgroup partial gradients of
 // the chunk (float4 columns), combined in LDS in a fixed order (deterministic).
+// (The plain single-GPU step of at most 64 partials keeps the sums in
+// registers instead, in the same order: reduce_apply_lanes.)
 // clip_by_norm needs the norm of the WHOLE tensor (tf_util.py:177-182): every
 // chunk publishes its fp64 sum of squares as two agent-scope 64-bit stores of
 // (epoch << 32 | half of the bits); all chunks of the tensor poll the pairs
@@ -204,13 +206,204 @@ __device__ __forceinline__ f32x4 red_tree(const f32x4 (*red)[64], int col) {
     return red_tree<LO, N / 2>(red, col) + red_tree<LO + N / 2, N / 2>(red, col);
 }
 
+// the four in-row steps of wave_sum_d: every lane ends with its 16-lane row's
+// sum, the same bits in all 16 (each step adds the same two operands on both
+// sides)
+__device__ __forceinline__ double row_sum_d(double v) {
+  v += dpp_d<0xB1, 0xf>(v);   // quad_perm [1,0,3,2]
+  v += dpp_d<0x4E, 0xf>(v);   // quad_perm [2,3,0,1]
+  v += dpp_d<0x141, 0xf>(v);  // row_half_mirror
+  v += dpp_d<0x140, 0xf>(v);  // row_mirror
+  return v;
+}
+
+// v + (v of lane ^ 16), then + (that of lane ^ 32), on gfx950's row / half
+// swaps (one VALU op each, no LDS crossbar round trip).  With both operands
+// the same register, v_permlane16_swap leaves the even row's value in one and
+// the odd row's in the other -- in every lane of the pair of rows -- and
+// v_permlane32_swap does the same for the two halves, so rows 0..3 holding
+// r0..r3 end with (r0 + r1) + (r2 + r3) in every lane, operand order included.
+// Every lane of the wave must be active.
+__device__ __forceinline__ float rows_sum(float v) {
+#if __has_builtin(__builtin_amdgcn_permlane16_swap) && __has_builtin(__builtin_amdgcn_permlane32_swap)
+  const auto p = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
+  v = __uint_as_float(p[0]) + __uint_as_float(p[1]);
+  const auto h = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
+  return __uint_as_float(h[0]) + __uint_as_float(h[1]);
+#else
+  const float o = __shfl_xor(v, 16, 64);
+  v = (threadIdx.x & 16) ? o + v : v + o;
+  const float u = __shfl_xor(v, 32, 64);
+  return (threadIdx.x & 32) ? u + v : v + u;
+#endif
+}
+
+// The tensor's sum of squares from the chunks' pairs, exactly as the LDS body
+// reads them: lane q takes chunk q's pair once both tags carry this step's
+// epoch (bounded spin -> *faulted and Ctl::fault = 1)
+__device__ __forceinline__ double chunks_poll(const uint64_t* part, int nch, uint32_t nep, int lane, uint32_t* fault,
+                                              bool* faulted) {
+  double tot = 0.0;
+  for (int q = lane; q < nch; q += 64) {
+    uint64_t hi = ld_agent64(part + 2 * q), lo = ld_agent64(part + 2 * q + 1);
+    uint32_t it = 0;
+    while ((uint32_t)(hi >> 32) != nep || (uint32_t)(lo >> 32) != nep) {
+      __builtin_amdgcn_s_sleep(1);
+      if (++it > kSpinLimit) {
+        __hip_atomic_store(fault, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        *faulted = true;
+        break;
+      }
+      hi = ld_agent64(part + 2 * q);
+      lo = ld_agent64(part + 2 * q + 1);
+    }
+    tot += __longlong_as_double((long long)((hi << 32) | (lo & 0xffffffffull)));
+  }
+  return wave_sum_d(tot);
+}
+
+// The chunk workgroup of the narrow launch (G = 4) with the reduced gradient
+// kept in registers: phase 0 and nwg <= 64 (host-checked, mdp_ra_lanes).  Wave
+// q owns parameters 64 q .. 64 q + 63 of the chunk and sums ALL the partials
+// for them: lane group g = lane >> 4 takes partials w = g + 4 k as 16-B loads
+// of parameters 64 q + 4 (lane & 15) .. + 3 -- the loads, their order and the
+// sum r_g are what wave g of the LDS body forms for these parameters -- and two
+// row swaps give (r0 + r1) + (r2 + r3) in every lane: the same bits without
+// the gradient's two LDS round trips and the one-wave section of the body
+// below.  Row q of the LDS body's wave 0 holds exactly wave q's parameters, so
+// the in-row steps of wave_sum_d give each wave its S_q, and the four meet in
+// LDS behind the one barrier as (S3 + S2) + (S1 + S0): the chunk's sum of
+// squares, published and polled as below.  (Publishing the four S_q as tagged
+// pairs of their own, with no barrier at all, measured slower: DESIGN.md
+// section 9.)
+__device__ __forceinline__ void reduce_apply_lanes(const FusedApplyArgs& f, const int b) {
+  const ApplyArgs& a = f.ap;
+  const int lane = threadIdx.x & 63;
+  const int wq = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const int g = lane >> 4;
+  int t = 0;
+  while (b >= f.rblk[t + 1]) ++t;
+  const TDesc td = a.net.t[t];
+  const int n = td.rows * td.cols;
+  const int nch = f.rblk[t + 1] - f.rblk[t];
+  const int c = b - f.rblk[t];
+  const int q0 = c * MDP_RA_CHUNK + 64 * wq;  // this wave's first parameter (tensor-relative)
+  const bool wact = q0 < n;                   // (uniform) a wave past the tensor's end has nothing to do
+  const int p0 = q0 + 4 * (lane & 15);        // the 4 parameters this lane sums
+  const bool act = p0 < n;
+  const int pq = p0 + g;                      // ... and the one it steps (component g of the four)
+  const bool aact = pq < n;
+  const int64_t iq = td.off + pq;
+  float m1 = 0.f, v1 = 0.f, th1 = 0.f, tg1 = 0.f;
+  const float b1p = a.beta[0], b2p = a.beta[1];  // this step's powers (advanced at the end)
+  const uint32_t nep = f.sync_ctr[7 * 32] + 1u;  // norm-handshake epoch (advanced at the end)
+  // a fault recorded by an earlier launch, read with the first loads and kept
+  // opaque until the step (as below)
+  const uint32_t fault0 = __hip_atomic_load(&a.ctl->fault, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  if (aact) {
+    m1 = a.m[iq];
+    v1 = a.v[iq];
+    th1 = a.theta[iq];
+    if (a.polyak) tg1 = a.target[iq];
+  }
+  f32x4 s = {0.f, 0.f, 0.f, 0.f};
+  if (act) {
+    // all 16 loads issued unconditionally; a partial past nwg re-reads the
+    // last one and is dropped by the select (as below)
+    const float* base = a.slab + (td.off - a.net.off) + p0;
+    f32x4 v[16];
+#pragma unroll
+    for (int k = 0; k < 16; ++k) v[k] = ld4(base + (int64_t)min(g + 4 * k, a.nwg - 1) * a.slab_stride);
+#pragma unroll
+    for (int k = 0; k < 16; ++k)
+      if (g + 4 * k >= a.nwg) v[k] = f32x4{0.f, 0.f, 0.f, 0.f};
+    s = ((v[0] + v[1]) + v[2]) + v[3];
+#pragma unroll
+    for (int k = 4; k < 16; ++k)
+      if (g + 4 * k < a.nwg) s += v[k];
+  }
+#pragma unroll
+  for (int j = 0; j < 4; ++j) s[j] = rows_sum(s[j]);
+#ifdef MDP_STAMPS
+  asm volatile("" ::"v"(s[0]), "v"(s[3]));  // (the stamp behind the sums, not beside the loads)
+#endif
+  MDP_RA_PH(1);
+  double ss = 0.0;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const float gs = s[j] * a.scale;
+    if (p0 + j < n) ss += (double)gs * (double)gs;
+  }
+  ss = row_sum_d(ss);
+  // Every wave drains its own loads (the beta powers, the epoch and the fault
+  // word were requested above) before the one barrier, so wave 0's arrival
+  // behind it speaks for all four whatever order they ran in.  A wave past the
+  // tensor's end brings 0, as its rows of the LDS body's wave 0 do.
+  __shared__ double sq_l[4];
+  asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+  if (lane == 0) sq_l[wq] = ss;
+  __syncthreads();
+  ss = (sq_l[3] + sq_l[2]) + (sq_l[1] + sq_l[0]);
+  MDP_RA_PH(2);
+  // the norm handshake's publish goes out first (its round trip is the
+  // launch's longest wait), the reduced gradient behind it
+  uint64_t* part = f.sync_part + (int64_t)t * MDP_RA_MAXCH * 2;
+  if (nch > 1 && threadIdx.x == 0) {
+    const uint64_t tag = (uint64_t)nep << 32;
+    const uint64_t bits = (uint64_t)__double_as_longlong(ss);
+    st_agent64(part + 2 * c, tag | (bits >> 32));
+    st_agent64(part + 2 * c + 1, tag | (bits & 0xffffffffull));
+  }
+  const float gq = g == 0 ? s[0] : g == 1 ? s[1] : g == 2 ? s[2] : s[3];
+  if (aact) a.grad[iq] = gq;
+  // arrival: this workgroup has its step's beta powers and epochs in
+  // registers, so the stats workgroup may advance them.  Behind the publish:
+  // the add goes to the one word every chunk workgroup adds to, and what a
+  // wave sends after it queues behind it (with the add in front of the publish
+  // the round was 1.3 % slower: DESIGN.md section 9)
+  if (a.stats_mode && threadIdx.x == 0)
+    __hip_atomic_fetch_add(f.done_ctr, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  MDP_RA_PH(3);
+  double tot = ss;
+  bool faulted = false;
+  if (wact) {
+    // every wave polls the tensor's pairs itself: no second barrier
+    if (nch > 1) tot = chunks_poll(part, nch, nep, lane, &a.ctl->fault, &faulted);
+    // a timed-out handshake of this wave or an earlier launch's fault leaves
+    // its parameters' optimizer state as it was (a wave that saw every word
+    // of its tensor has the right norm and steps)
+    faulted = __ballot(faulted || ctr_use(fault0) != 0u) != 0ull;
+  }
+  const float norm = (float)sqrt(tot);
+  MDP_RA_PH(4);
+  // TF1 ApplyAdam (+ Polyak for the actor step) of this lane's parameter
+  if (aact && !faulted) {
+    const float clip = a.clip;
+    const float denom = fmaxf(norm, clip);
+    const float one = 1.0f;
+    const float alpha = a.lr * sqrtf(one - b2p) / (one - b1p);
+    const float c1 = one - a.b1, c2 = one - a.b2;
+    const float gc = ((gq * a.scale) * clip) / denom;
+    const float mo = m1 + (gc - m1) * c1;
+    const float vo = v1 + (gc * gc - v1) * c2;
+    const float tho = th1 - (mo * alpha) / (sqrtf(vo) + a.eps);
+    a.m[iq] = mo;
+    a.v[iq] = vo;
+    a.theta[iq] = tho;
+    if (a.polyak) a.target[iq] = a.pa * tg1 + a.pb * tho;
+  }
+}
+
 // b: this workgroup's index among the nb workgroups of this net's step;
 // G waves (G = 16: 1024-thread workgroups; G = 4: 256 threads, used exactly
 // when nwg <= 64 -- a launch of fewer waves dispatches sooner).  Wave q sums
 // partials w = q, q + G, ..., then a fixed tree over the waves: the summation
-// order is a function of nwg alone (every launch of a configuration agrees)
-template <int G>
+// order is a function of nwg alone (every launch of a configuration agrees).
+// LANES (G = 4, phase 0): the chunk workgroups run reduce_apply_lanes instead
+// -- the same sums in the same order, the gradient kept in registers
+template <int G, bool LANES = false>
 __device__ __forceinline__ void reduce_apply_body(const FusedApplyArgs& f, const int b, const uint32_t nb) {
+  static_assert(!LANES || G == 4, "the register body is a narrow launch");
   const ApplyArgs& a = f.ap;
   __shared__ f32x4 red[G][64];
   __shared__ f32x4 gl[64];         // the chunk's reduced gradient (wave 0 -> the Adam waves)
@@ -219,7 +412,9 @@ __device__ __forceinline__ void reduce_apply_body(const FusedApplyArgs& f, const
   MDP_STAMP(30);
   MDP_RA_PH(0);
   if (f.phase == 1 && b >= f.rblk[6]) return;  // reduce-only pass: chunk workgroups only
-  if (b < f.rblk[6]) {
+  if (LANES && b < f.rblk[6]) {
+    reduce_apply_lanes(f, b);
+  } else if (b < f.rblk[6]) {
     int t = 0;
     while (b >= f.rblk[t + 1]) ++t;
     const TDesc td = a.net.t[t];
@@ -559,7 +754,7 @@ extern "C" int mdp_debug_ra_wg(unsigned long long* t0, unsigned long long* t1, i
 #endif
 
 
-template <int NT>
+template <int NT, bool LANES = false>
 __global__ __launch_bounds__(NT) void k_reduce_apply(FusedApplyArgs f) {
   MDP_RA_WG(g_ra_t0);
   MDP_TL(f.ap.ctl, f.ap.polyak ? 3 : 1, blockIdx.x == gridDim.x - 1 && f.pf_count > 0 ? 3 : 0);
@@ -572,7 +767,7 @@ __global__ __launch_bounds__(NT) void k_reduce_apply(FusedApplyArgs f) {
     MDP_RA_WG(g_ra_t1);
     return;
   }
-  reduce_apply_body<NT / 64>(f, blockIdx.x, gridDim.x - (f.pf_count > 0 ? 1 : 0));
+  reduce_apply_body<NT / 64, LANES>(f, blockIdx.x, gridDim.x - (f.pf_count > 0 ? 1 : 0));
 #ifdef MDP_STAMPS
   __syncthreads();
   MDP_RA_WG(g_ra_t1);
@@ -581,7 +776,7 @@ __global__ __launch_bounds__(NT) void k_reduce_apply(FusedApplyArgs f) {
 
 // throughput mode: the steps of several nets in one launch (each net's chunk
 // workgroups handshake only among themselves; the nets are independent)
-template <int NT>
+template <int NT, bool LANES = false>
 __global__ __launch_bounds__(NT) void k_reduce_apply_batch(RaBatch rb) {
   if (rb.pf_count > 0 && blockIdx.x == gridDim.x - 1) {  // a piece of the next round's index draw
     make_index_block<NT>(rb.pf_ctl, rb.pf_count, rb.pf_out);
@@ -590,7 +785,7 @@ __global__ __launch_bounds__(NT) void k_reduce_apply_batch(RaBatch rb) {
   int q = 0;
   while (q + 1 < rb.count && (int)blockIdx.x >= rb.wg_start[q + 1]) ++q;
   const int b = blockIdx.x - rb.wg_start[q];
-  reduce_apply_body<NT / 64>(rb.list[q], b, (uint32_t)(rb.wg_start[q + 1] - rb.wg_start[q]));
+  reduce_apply_body<NT / 64, LANES>(rb.list[q], b, (uint32_t)(rb.wg_start[q + 1] - rb.wg_start[q]));
 }
 
 int mdp_ra_grid(const FusedApplyArgs& f) {
@@ -602,14 +797,18 @@ int mdp_ra_grid(const FusedApplyArgs& f) {
 // most 64 partials: S2 optimizer launch 3.88 -> 3.50 us event-timed (128
 // threads: 4.17, 512: 3.64).  MDP_RA_NARROW=0 builds the 1024-thread launch
 // for every fan-in (A/B only: its summation order differs)
-#ifndef MDP_RA_NARROW
-#define MDP_RA_NARROW 1
-#endif
 static bool mdp_ra_narrow(const FusedApplyArgs& f) { return MDP_RA_NARROW && f.ap.nwg <= 64; }
 
-hipError_t mdp_launch_reduce_apply(const FusedApplyArgs& f, hipStream_t s) {
+// the narrow launch may keep the reduced gradient in registers
+// (reduce_apply_lanes): the plain fused step; the reduce-only pass, the step
+// from an all-reduced gradient and the xGMI exchange keep the LDS body
+bool mdp_ra_lanes(const FusedApplyArgs& f) { return mdp_ra_narrow(f) && f.phase == 0; }
+
+hipError_t mdp_launch_reduce_apply(const FusedApplyArgs& f, hipStream_t s, bool lanes) {
   const dim3 grid(mdp_ra_grid(f) + (f.pf_count > 0 ? 1 : 0));
-  if (mdp_ra_narrow(f))
+  if (lanes && mdp_ra_lanes(f))
+    mdp_launch(k_reduce_apply<256, true>, grid, dim3(256), 0, s, f);
+  else if (mdp_ra_narrow(f))
     mdp_launch(k_reduce_apply<256>, grid, dim3(256), 0, s, f);
   else
     mdp_launch(k_reduce_apply<1024>, grid, dim3(1024), 0, s, f);
@@ -625,6 +824,7 @@ hipError_t mdp_launch_reduce_apply(const FusedApplyArgs& f, hipStream_t s) {
 hipError_t mdp_spin_kernels_scratch(int* bytes) {
   const void* ks[] = {(const void*)k_reduce_apply<256>, (const void*)k_reduce_apply<1024>,
                       (const void*)k_reduce_apply_batch<256>, (const void*)k_reduce_apply_batch<1024>,
+                      (const void*)k_reduce_apply<256, true>, (const void*)k_reduce_apply_batch<256, true>,
                       (const void*)k_xchg_probe};
   *bytes = 0;
   for (const void* k : ks) {
@@ -648,7 +848,9 @@ hipError_t mdp_ra_batch_occupancy(int* per_cu) {
 
 hipError_t mdp_launch_reduce_apply_batch(const RaBatch& b, hipStream_t s) {
   const dim3 grid(b.wg_start[b.count] + (b.pf_count > 0 ? 1 : 0));  // + the draw piece, last
-  if (MDP_RA_NARROW && b.narrow)
+  if (MDP_RA_NARROW && b.narrow == 2)
+    mdp_launch(k_reduce_apply_batch<256, true>, grid, dim3(256), 0, s, b);
+  else if (MDP_RA_NARROW && b.narrow)
     mdp_launch(k_reduce_apply_batch<256>, grid, dim3(256), 0, s, b);
   else
     mdp_launch(k_reduce_apply_batch<1024>, grid, dim3(1024), 0, s, b);

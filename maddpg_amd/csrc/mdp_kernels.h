@@ -218,6 +218,9 @@ struct ApplyArgs {
 };
 
 // k_reduce_apply (mdp_apply_fused.hip): batch reduction + optimizer step in one launch
+#ifndef MDP_RA_NARROW
+#define MDP_RA_NARROW 1   // (mdp_apply_fused.hip, mdp_ra_narrow; k_reduce follows the same rule)
+#endif
 #define MDP_RA_CHUNK 256   // parameters per workgroup
 #define MDP_RA_MAXCH 256   // chunks per tensor the sync area holds
 // Direct xGMI gradient exchange of the data-parallel step (phase 3 below):
@@ -631,14 +634,17 @@ hipError_t mdp_launch_eval_reset(const EnvDesc& env, uint64_t seed, uint32_t fir
                                  int32_t* goal, hipStream_t s);
 hipError_t mdp_launch_apply(const ApplyArgs& a, hipStream_t s);
 hipError_t mdp_launch_reduce(const ReduceArgs& a, hipStream_t s);
-hipError_t mdp_launch_reduce_apply(const FusedApplyArgs& f, hipStream_t s);
+// lanes: the host allows the narrow launch's register body where mdp_ra_lanes(f) holds
+hipError_t mdp_launch_reduce_apply(const FusedApplyArgs& f, hipStream_t s, bool lanes);
+bool mdp_ra_lanes(const FusedApplyArgs& f);
 // throughput mode: the optimizer steps of `count` nets in one launch; list[]
 // lives in device memory (written once), wg_start[q] = first workgroup of net q
 #define MDP_RA_BATCH_MAX (2 * MDP_MAX_AGENTS)
 struct RaBatch {
   const FusedApplyArgs* list = nullptr;
   int count = 0;
-  int narrow = 0;       // fan-in <= 64 partials: 256-thread workgroups (mdp_ra_narrow)
+  int narrow = 0;       // fan-in <= 64 partials: 256-thread workgroups (mdp_ra_narrow);
+                        // 2: ... with the register body (mdp_ra_lanes holds for every net of list[])
   int wg_start[MDP_RA_BATCH_MAX + 1] = {};
   // pf_count > 0: one extra (last) workgroup draws pf_count indices of the next
   // round into pf_out, continuing the MT19937 stream in pf_ctl (as FusedApplyArgs)

@@ -232,13 +232,20 @@ __device__ inline bool last_block(uint32_t* ticket) {
 }
 }  // namespace
 
-// grad[e] = sum_w slab[w][e] in fixed w order (deterministic); one element per
-// thread, the nwg partial loads unrolled 8-wide so they are in flight together.
+// grad[e] = sum_w slab[w][e] in the fused launch's order (reduce_apply_body,
+// mdp_apply_fused.hip), so the fused and the unfused step of one state are the
+// same step bit for bit: G lanes per element (G = 4 up to 64 partials, else
+// 16, as the fused launch picks its workgroup), lane q sums partials w = q +
+// G k as ((v0 + v1) + v2) + v3, then v4, v5, ... (the first 16 loads in flight
+// together), and the G sums meet in the fixed pairwise tree (r0 + r1) + (r2 +
+// r3), ... on DPP moves.
 // Thread 0 also advances the optimizer step (replaces the AdamOptimizer._finish
 // beta-power update): beta[2..3] <- beta[0..1] (powers this step's ApplyAdam
 // uses), beta[0..1] *= (b1, b2) in fp32.  k_reduce always precedes k_apply in
 // stream order, so no cross-workgroup protocol is needed.
+template <int G>
 __global__ __launch_bounds__(256) void k_reduce(ReduceArgs a) {
+  static_assert(G == 4 || G == 16, "the fused launch's 4 or 16 waves");
   const int64_t e = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
   if (e == 0 && a.beta) {
     const float p1 = a.beta[0], p2 = a.beta[1];
@@ -248,32 +255,24 @@ __global__ __launch_bounds__(256) void k_reduce(ReduceArgs a) {
     a.beta[1] = p2 * a.b2;
     if (a.bump_ctr) a.ctl->upd_ctr += 1u;
   }
-  // 8 lanes per element: lane q sums partials w = q, q+8, ... (all loads in
-  // flight at once), then a fixed xor-tree over the 8 lanes -> deterministic
-  const int64_t el = e >> 3;
-  const int q = (int)(e & 7);
+  const int64_t el = e / G;
+  const int q = (int)(e & (G - 1));
   float s = 0.f;
   if (el < a.size) {
     const float* p = a.slab + el;
-    float v[8], t[24];  // up to 32 partials per lane (B <= 4096) in flight at once
+    float v[16];
 #pragma unroll
-    for (int k = 0; k < 8; ++k) {
-      const int w = q + 8 * k;
+    for (int k = 0; k < 16; ++k) {
+      const int w = q + G * k;
       v[k] = w < a.nwg ? p[(int64_t)w * a.slab_stride] : 0.f;
     }
+    s = ((v[0] + v[1]) + v[2]) + v[3];
 #pragma unroll
-    for (int k = 0; k < 24; ++k) {
-      const int w = q + 64 + 8 * k;
-      t[k] = w < a.nwg ? p[(int64_t)w * a.slab_stride] : 0.f;
-    }
-#pragma unroll
-    for (int k = 0; k < 24; ++k)
-      if (q + 64 + 8 * k < a.nwg) s += t[k];
-    for (int w = q + 256; w < a.nwg; w += 8) s += p[(int64_t)w * a.slab_stride];
-#pragma unroll
-    for (int k = 0; k < 8; ++k) s += v[k];
+    for (int k = 4; k < 16; ++k)
+      if (q + G * k < a.nwg) s += v[k];
+    for (int w = q + 16 * G; w < a.nwg; w += G) s += p[(int64_t)w * a.slab_stride];
   }
-  s = half_row_sum(s);
+  s = G == 4 ? quad_sum(s) : row_sum(s);
   if (el < a.size && q == 0) a.grad[a.off + el] = s;
 }
 
@@ -1528,8 +1527,10 @@ hipError_t mdp_launch_apply(const ApplyArgs& a, hipStream_t s) {
   return hipSuccess;
 }
 hipError_t mdp_launch_reduce(const ReduceArgs& a, hipStream_t s) {
-  const int grid = (int)((a.size * 8 + 255) / 256);
-  mdp_launch(k_reduce, dim3(grid), dim3(256), 0, s, a);
+  if (MDP_RA_NARROW && a.nwg <= 64)  // (the fused launch's rule, mdp_ra_narrow)
+    mdp_launch(k_reduce<4>, dim3((int)((a.size * 4 + 255) / 256)), dim3(256), 0, s, a);
+  else
+    mdp_launch(k_reduce<16>, dim3((int)((a.size * 16 + 255) / 256)), dim3(256), 0, s, a);
   MDP_CHECK_LAUNCH();
   return hipSuccess;
 }

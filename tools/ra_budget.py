@@ -11,6 +11,10 @@ last actor-step optimizer launch of a graph-replayed round, s_memrealtime
   handshake done (every chunk of the tensor seen) | 5 Adam (+ Polyak) stores
   issued (chunk workgroups end) ; stats workgroup: 5 stats written | 6 every
   chunk workgroup arrived | 7 beta powers / epochs advanced (its end).
+In the register body (reduce_apply_lanes; MDP_RA_LANES=0 stamps the LDS body
+instead) the same points read: 1 partials loaded and summed in registers (row
+swaps done) | 2 the four waves' sums of squares met in LDS (one barrier) | 3
+norm published, reduced gradient stored, arrival add issued | 4, 5 as above.
 Durations per launch from HIP events on the launch's own dispatch packet (the
 interval rocprof reports) in an eager pass of the same rounds are printed
 beside the in-kernel span: the difference is the dispatch + completion

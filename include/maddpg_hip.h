@@ -700,6 +700,12 @@ int mdp_prof_enable(mdp_handle* h, int32_t kind, int32_t on);
 /* which grad kernels serve `agent`: 1 = register-resident k_*_grad_r (H = 64
  * envelope), 0 = general k_*_grad */
 int mdp_grad_variant(mdp_handle* h, int32_t agent);
+/* workgroups per 16-row tile of the strict-mode k_critic_grad_r launch, decided
+ * at mdp_create: 2 (twins, each forming half of the tile's weight-gradient
+ * tiles; same results bit for bit) while 3 x ceil(batch / 16) + 1 workgroups
+ * find a compute unit each, else 1; MDP_GRAD_TWIN=0 in the environment at
+ * create: always 1.  Throughput mode and the general kernels launch one. */
+int mdp_grad_twin(mdp_handle* h);
 /* sum of event-measured durations (ms) and launch count since enable; synchronises */
 int mdp_prof_read(mdp_handle* h, int32_t kind, double* total_ms, int64_t* launches);
 

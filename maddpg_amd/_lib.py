@@ -128,6 +128,7 @@ SIGNATURES = {
     "mdp_train_step": (ctypes.c_int, [_P, _I32]),
     "mdp_dp_unique_id": (ctypes.c_int, [ctypes.c_char_p]),
     "mdp_grad_variant": (ctypes.c_int, [_P, _I32]),
+    "mdp_grad_twin": (ctypes.c_int, [_P]),
     "mdp_dp_init": (ctypes.c_int, [_P, ctypes.c_char_p, _I32, _I32]),
     "mdp_dp_xgmi_open": (ctypes.c_int, [_P, _I32, _I32, ctypes.c_char_p]),
     "mdp_dp_xgmi_connect": (ctypes.c_int, [_P, ctypes.c_char_p]),

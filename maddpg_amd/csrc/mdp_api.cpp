@@ -337,6 +337,11 @@ struct mdp_handle {
   // ... with the reduced gradient kept in registers where mdp_ra_lanes allows
   // (MDP_RA_LANES=0: the LDS body for every launch -- tests and A/B runs)
   bool ra_lanes = true;
+  // strict order, register kernels: two workgroups per critic row tile, each
+  // forming half of the tile's weight-gradient tiles (CriticArgs::twin), when
+  // the doubled grid still has a CU per workgroup -- decided at create
+  // (MDP_GRAD_TWIN=0: one workgroup per tile -- tests and A/B runs)
+  bool grad_twin = true;
   uint32_t* ra_ctr = nullptr;
   uint64_t* ra_part = nullptr;
   // the actor forward + sample of agent i computed by extra workgroups of its
@@ -772,6 +777,7 @@ CriticArgs critic_args(mdp_handle* h, int agent, const int32_t* idx, const float
   a.apre_rows = h->apre_rows;
   a.cpre_prev = post_prev;
   a.multi = tp ? 2 : 0;
+  a.twin = 1;
   a.slab_agent_stride = 0;
   a.pf_ctl = h->ctl;
   a.pf_out = nullptr;
@@ -841,6 +847,7 @@ int do_critic_grad(mdp_handle* h, int agent, const int32_t* idx, const float* u_
     }
     if (apre) a.apre = h->apre;
     if (post_prev >= 0) a.cpre = h->cpre;
+    if (h->grad_twin) a.twin = 2;
     if (h->per)
       HIPCHK(h, mdp_launch_critic_grad_r_per(per_critic_args(h, a), lds_critic_r_bytes(h->L.topo, agent), h->stream));
     else
@@ -1583,6 +1590,7 @@ int tp_grads_fast(mdp_handle* h, const int32_t* idx, const float* u_tgt, const f
     a.slab_stat = h->stat_c;
     a.y_out = h->y;
     a.group = 0;
+    a.twin = 1;
     a.multi = n;
     a.slab_agent_stride = nwg * h->L.slab_c;
     ProfScope p(h, MDP_K_CRITIC_GRAD);
@@ -2000,6 +2008,8 @@ int mdp_create(const mdp_config* cfg, void* arena_dev, int64_t arena_bytes, void
     h->fused_apply = !(u && u[0] == '1');
     const char* rl = getenv("MDP_RA_LANES");
     h->ra_lanes = !(rl && rl[0] == '0');
+    const char* gt = getenv("MDP_GRAD_TWIN");
+    h->grad_twin = !(gt && gt[0] == '0');
     const char* rd = getenv("MDP_ROLLOUT_DRAW");
     h->rollout_draw = !(rd && rd[0] == '0');
     const char* da = getenv("MDP_DRAW_AHEAD");
@@ -2032,6 +2042,10 @@ int mdp_create(const mdp_config* cfg, void* arena_dev, int64_t arena_bytes, void
     int scratch = 0;
     HIPCHK(h, mdp_spin_kernels_scratch(&scratch));
     if (scratch > 0) h->ra_cap = h->ra_batch_cap = 0;
+    // twin critic workgroups only while the launch's whole grid (both twins of
+    // every row tile, the actor_pre tiles, the draw) finds a CU of its own: a
+    // 512-thread workgroup of k_critic_grad_r fills one
+    if (2 * h->L.nwg + h->L.nwg + 1 > cus) h->grad_twin = false;
   }
   if (hip_stream) {
     h->stream = (hipStream_t)hip_stream;
@@ -2603,6 +2617,11 @@ int mdp_update_round(mdp_handle* h) {
 int mdp_grad_variant(mdp_handle* h, int32_t agent) {
   if (unusable(h) || agent < 0 || agent >= h->cfg.n_agents) return -1;
   return (!h->general_grads && grads_r_ok(h->L.topo, agent)) ? 1 : 0;
+}
+
+int mdp_grad_twin(mdp_handle* h) {
+  if (unusable(h)) return -1;
+  return h->grad_twin ? 2 : 1;
 }
 
 int mdp_dp_unique_id(uint8_t* out128) {

@@ -1173,13 +1173,15 @@ __device__ __forceinline__ void wgrad_multi(const WgJob& j0, const WgJob& j1, co
       if (krem[s]) slab_st4(dst[s], acc[s]);
   }
 }
-__device__ __forceinline__ void wgrad_waves(const float* X, int ldx, int K, const float* dY, int ldy, int N,
-                                            float* __restrict__ dW, int w0, int wn) {
-  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  if (wave < w0 || wave >= w0 + wn) return;
+// The tiles of dW[K][N] dealt round-robin over `vn` virtual waves, this wave
+// being number `vw` of them: tiles vw, vw + vn, ...  (The waves may belong to
+// more than one workgroup holding the same operands -- k_critic_grad_r's twins.)
+__device__ __forceinline__ void wgrad_vwaves(const float* X, int ldx, int K, const float* dY, int ldy, int N,
+                                             float* __restrict__ dW, int vw, int vn) {
+  const int lane = threadIdx.x & 63;
   const int r = lane & 15, kq = lane >> 4;
   const int nmt = (K + 15) >> 4, nnt = N >> 4;
-  for (int t = wave - w0; t < nmt * nnt; t += wn) {
+  for (int t = vw; t < nmt * nnt; t += vn) {
     const int mt = t / nnt, nt = t - mt * nnt;
     const int feat = mt * 16 + r;
     const int fc = min(feat, K - 1);
@@ -1194,5 +1196,12 @@ __device__ __forceinline__ void wgrad_waves(const float* X, int ldx, int K, cons
     }
     if (feat < K) slab_st4(dW + feat * N + nt * 16 + kq * 4, acc);
   }
+}
+// ... over waves [w0, w0 + wn) of this workgroup
+__device__ __forceinline__ void wgrad_waves(const float* X, int ldx, int K, const float* dY, int ldy, int N,
+                                            float* __restrict__ dW, int w0, int wn) {
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  if (wave < w0 || wave >= w0 + wn) return;
+  wgrad_vwaves(X, ldx, K, dY, ldy, N, dW, wave - w0, wn);
 }
 

@@ -23,7 +23,8 @@
 //                  wave 4: head q', fp64 TD, dL/dq (-> LDS flag), d2, dW3, db3 | B5
 //   waves 0..3     v = W3 o [h2 > 0] rows | B3 | u tile = (v W2^T) o [h1 > 0] | B4 |
 //                  wait for dq, dh1 tile = dq o u | B5   (the backward is linear in dq)
-//   all            dW2, db2, dW1, db1 (one phase)
+//   all            dW2, db2, dW1, db1 (one phase; with twin workgroups, CriticArgs::twin,
+//                  each of the row tile's two workgroups forms half of these tiles)
 // k_actor_grad_r (maddpg.py:37-58):
 //   wave 0  actor forward, Gumbel a_i                              | B2
 //   waves 1..3  critic L1 on the replay part (a_i rows masked), one third of
@@ -59,7 +60,9 @@
 // for the GPU: slots 64, 65), which places it in the launch and calibrates the
 // shader clock.
 #define MDP_BUD_N 72
-__device__ unsigned long long g_bud[2][160][MDP_BUD_N];
+// (workgroups: 64 critic tiles, their 64 twins, 64 actor_pre and the draw at B = 1024)
+#define MDP_BUD_WG 256
+__device__ unsigned long long g_bud[2][MDP_BUD_WG][MDP_BUD_N];
 __shared__ int s_bud;  // this launch records into g_bud[s_bud] (-1: not the chosen agent's launch)
 __shared__ unsigned long long s_bud_t[MDP_BUD_N];
 __shared__ unsigned s_bud_cnt;
@@ -115,7 +118,7 @@ __device__ __forceinline__ unsigned long long bud_real() { return __builtin_amdg
     unsigned c__ = 0u;                                                                    \
     if ((threadIdx.x & 63) == 0) c__ = atomicAdd(&s_bud_cnt, 1u);                         \
     c__ = __builtin_amdgcn_readfirstlane(c__);                                            \
-    if (c__ + 1u == (blockDim.x >> 6) && s_bud >= 0 && blockIdx.x < 160) {                \
+    if (c__ + 1u == (blockDim.x >> 6) && s_bud >= 0 && blockIdx.x < MDP_BUD_WG) {                \
       const int l__ = threadIdx.x & 63;                                                   \
       g_bud[s_bud][blockIdx.x][l__] = s_bud_t[l__];                                       \
       if (l__ < MDP_BUD_N - 64) g_bud[s_bud][blockIdx.x][64 + l__] = s_bud_t[64 + l__];   \
@@ -149,11 +152,11 @@ __device__ unsigned long long g_wg_t0[2][512];
 __device__ unsigned long long g_wg_t1[2][512][8];
 // critic_pre's per-wave phase points (row tile < 64, wave, point)
 __device__ unsigned long long g_cpre_t[64][8][6];
-// the critic step's per-wave points after B5 (row tile < 64, wave, point)
+// the critic step's per-wave points after B5 (row tile < 64, wave, point; of twins, half 0's)
 __device__ unsigned long long g_crit_t[64][8][6];
 #define CRIT_T(i)                                                                                   \
   do {                                                                                              \
-    if ((threadIdx.x & 63) == 0 && bx < 64) g_crit_t[bx][threadIdx.x >> 6][i] = __builtin_amdgcn_s_memrealtime(); \
+    if ((threadIdx.x & 63) == 0 && bx < 64 && half == 0) g_crit_t[bx][threadIdx.x >> 6][i] = __builtin_amdgcn_s_memrealtime(); \
   } while (0)
 #define CPRE_T(i)                                                                                   \
   do {                                                                                              \
@@ -550,14 +553,35 @@ __global__ __launch_bounds__(512) void k_critic_grad_r(A a) {
   __shared__ int post_sync[2];  // critic_post: target-actor L1, L2 tiles of waves 0..3 done
   __shared__ int dq_ready;      // wave 4 wrote dL/dq (the dh1 tiles of waves 0..3 wait for it)
   int agent = a.agent, bx = blockIdx.x;
-  if (a.apre) {  // workgroups [B/16, 2 B/16): the actor step's forward (strict mode only)
-    const int nwg = (a.B + MDP_RW - 1) / MDP_RW;
-    if (bx >= nwg) {
+  // grid: B/16 critic workgroups | with twins their B/16 second halves |
+  // B/16 actor_pre workgroups (a.apre) | the draw
+  const int twin = a.twin;
+  if (a.apre) {  // the actor step's forward (strict mode only)
+    const int ncw = twin * ((a.B + MDP_RW - 1) / MDP_RW);
+    if (bx >= ncw) {
       MDP_TL_ROLE(0, 1);
-      actor_pre_tile<NARROW>(a, lds, &rows_ready, bx - nwg);
+      actor_pre_tile<NARROW>(a, lds, &rows_ready, bx - ncw);
       MDP_WG_END(0);
       return;
     }
+  }
+  // twins (strict mode only): workgroups t and B/16 + t both run row tile t up
+  // to B5 -- the same loads and chains, so both hold the same d2, d1, h1c and
+  // rows in LDS -- and then each forms its half of the weight-gradient tiles.
+  // What belongs to the row tile (TD targets, stats, dW3 / db3) is stored by
+  // half 0 alone: every word has one writer.
+  // Not 2 t and 2 t + 1: workgroups go round the 8 XCDs in turn, so at B/16 a
+  // multiple of 8 both twins of tile t sit on the XCD of the critic_pre
+  // workgroup that wrote its cpre block and rows (workgroup B/16 + t of the
+  // actor launch) and read them from that XCD's L2, as the single workgroup
+  // did.  Adjacent twins read them on two other XCDs, and the actor launch's
+  // end-of-kernel write-back of those blocks, then shared across XCDs, took
+  // 0.77 us longer -- more than the halved tail gives
+  int half = 0;
+  if (twin > 1) {
+    const int nwg = (a.B + MDP_RW - 1) / MDP_RW;
+    half = bx >= nwg ? 1 : 0;
+    bx -= half * nwg;
   }
   if (a.multi > 1) {  // throughput mode: every agent's critic step in this launch
     const int nwg = (a.B + MDP_RW - 1) / MDP_RW;
@@ -923,12 +947,12 @@ __global__ __launch_bounds__(512) void k_critic_grad_r(A a) {
           const float w = a.is_w[r0 + lane];
           g = ((2.0f * diff) * w) * a.inv_b;
           s_l = (double)w * s_l;
-          a.td_out[r0 + lane] = fabsf(diff);
+          if (half == 0) a.td_out[r0 + lane] = fabsf(diff);
         }
         s_y = y64;
         s_r = rew;
         s_q = qnv;
-        y_out[r0 + lane] = y64;
+        if (half == 0) y_out[r0 + lane] = y64;
       }
       if (lane < MDP_R) dq[lane] = g;
       lds_signal(&dq_ready);
@@ -944,13 +968,15 @@ __global__ __launch_bounds__(512) void k_critic_grad_r(A a) {
         d2[rr * LD + lane] = h > 0.f ? dqr * w3c : 0.f;
       }
       MDP_STAMPW(61);
-      slab_st(slab + nd.t[4].off + lane, s);
-      if (lane == 0) slab_st(slab + nd.t[5].off, sb);
+      if (half == 0) {
+        slab_st(slab + nd.t[4].off + lane, s);
+        if (lane == 0) slab_st(slab + nd.t[5].off, sb);
+      }
       MDP_STAMPW(7);
     }
     __syncthreads();  // B5
-    if (tt == 0) {
-      MDP_STAMPW(8);
+    if (tt == 0) MDP_STAMPW(8);
+    if (tt == 0 && half == 0) {
       // the update's stats (maddpg.py:196): partial sums of this tile, beside the backward
       s_l = sum16(s_l);
       s_y = sum16(s_y);
@@ -970,16 +996,23 @@ __global__ __launch_bounds__(512) void k_critic_grad_r(A a) {
   // interleaved, stores last -- measured slower: S2 1.074M -> 1.048M with all
   // five tiles of a wave at once, 1.064M as 2 + 3: the stores of the first
   // tiles no longer drain behind the later tiles' work)
+  // Twins: the tiles are dealt over the 16 waves of the pair, wave w of half h
+  // being number w + 8 h -- what sets this tail is the number of tiles a wave
+  // runs back to back (each a dependent chain of four MFMAs), 4 or 5 on one
+  // workgroup and 2 or 3 on two.  Numbers 0..3 take the third tile, so the
+  // half 0, dispatched B/16 workgroups earlier, forms 20 of the 36 and half 1,
+  // 16 and the two column sums (on waves with two tiles).
+  const int vw = wave + 8 * half, vn = 8 * twin;
   CRIT_T(0);
-  wgrad_waves(h1c, LH, RH, d2, LD, RH, slab + nd.t[2].off, 0, 8);
+  wgrad_vwaves(h1c, LH, RH, d2, LD, RH, slab + nd.t[2].off, vw, vn);
   CRIT_T(1);
-  wgrad_waves(rowbuf + xo_c, ldr, ka_c, d1, LD, RH, slab + nd.t[0].off, 0, 8);
+  wgrad_vwaves(rowbuf + xo_c, ldr, ka_c, d1, LD, RH, slab + nd.t[0].off, vw, vn);
   CRIT_T(2);
-  if (kb_c) wgrad_waves(rowbuf + ag.act_off, ldr, kb_c, d1, LD, RH, slab + nd.t[0].off + ka_c * RH, 0, 8);
+  if (kb_c) wgrad_vwaves(rowbuf + ag.act_off, ldr, kb_c, d1, LD, RH, slab + nd.t[0].off + ka_c * RH, vw, vn);
   CRIT_T(3);
   if (wave == 4) MDP_STAMPW(9);
-  if (wave == 5) colsum64(d2, LD, slab + nd.t[3].off);
-  if (wave == 7) colsum64(d1, LD, slab + nd.t[1].off);
+  if (vw == vn - 3) colsum64(d2, LD, slab + nd.t[3].off);
+  if (vw == vn - 1) colsum64(d1, LD, slab + nd.t[1].off);
   CRIT_T(4);
   MDP_STAMP(10);
   MDP_WG_END(0);
@@ -1237,16 +1270,22 @@ bool topo_narrow(const Topo& t) {
     if (topo_act_w(t, j) != MDP_ACT_DIM) return true;
   return false;
 }
+// the critic launch's workgroups beside its first row_tiles(B) x multi: the
+// second twins (strict mode only: multi <= 1), actor_pre, the draw
+int critic_extra(const CriticArgs& a) {
+  return (a.twin > 1 && a.multi <= 1 ? row_tiles(a.B) : 0) + (a.apre ? row_tiles(a.B) : 0) + (a.pf_count > 0 ? 1 : 0);
+}
 }  // namespace
 
 hipError_t mdp_launch_critic_grad_r(const CriticArgs& a, int lds_bytes, hipStream_t s) {
-  // grid: critic row tiles | actor-forward row tiles (a.apre) | the index draw (pf_count; last)
-  const int extra = (a.apre ? row_tiles(a.B) : 0) + (a.pf_count > 0 ? 1 : 0);
+  // grid: critic row tiles | their second twins (a.twin) | actor-forward row
+  // tiles (a.apre) | the index draw (pf_count; last)
+  const int extra = critic_extra(a);
   if (topo_narrow(a.topo)) return launch_r<k_critic_grad_r<false, true, CriticArgs>>(a, lds_bytes, s, extra);
   return launch_r<k_critic_grad_r<false, false, CriticArgs>>(a, lds_bytes, s, extra);
 }
 hipError_t mdp_launch_critic_grad_r_per(const CriticArgsPer& a, int lds_bytes, hipStream_t s) {
-  const int extra = (a.apre ? row_tiles(a.B) : 0) + (a.pf_count > 0 ? 1 : 0);
+  const int extra = critic_extra(a);
   if (topo_narrow(a.topo)) return launch_r<k_critic_grad_r<true, true, CriticArgsPer>>(a, lds_bytes, s, extra);
   return launch_r<k_critic_grad_r<true, false, CriticArgsPer>>(a, lds_bytes, s, extra);
 }
@@ -1270,9 +1309,9 @@ extern "C" int mdp_debug_tl_r(unsigned long long* out, int reset) {
 #endif
 
 #ifdef MDP_BUDGET
-// [2][160][MDP_BUD_N] phase points of the chosen agent's last critic / actor launch; reset: zero them
+// [2][MDP_BUD_WG][MDP_BUD_N] phase points of the chosen agent's last critic / actor launch; reset: zero them
 extern "C" int mdp_debug_budget(unsigned long long* out, int reset) {
-  const size_t n = sizeof(unsigned long long) * 2 * 160 * MDP_BUD_N;
+  const size_t n = sizeof(unsigned long long) * 2 * MDP_BUD_WG * MDP_BUD_N;
   if (reset) {
     void* p = nullptr;
     if (hipGetSymbolAddress(&p, HIP_SYMBOL(g_bud)) != hipSuccess) return -1;

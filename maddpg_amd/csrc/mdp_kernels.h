@@ -31,6 +31,12 @@ struct CriticArgs {
   double* slab_stat;    // [nwg][8]
   double* y_out;        // [B]
   int group;            // target actors run concurrently per pass (LDS budget)
+  // k_critic_grad_r only: workgroups per critic row tile, 1 or 2.  With 2 (twins,
+  // strict mode when the doubled grid still has a CU per workgroup) both run the
+  // tile's step up to B5 from the same inputs and each forms half of its
+  // weight-gradient tiles; every slab word keeps its one writer and its chain
+  // (here: the word was padding, every other field keeps its offset)
+  int twin;
   // k_critic_grad_r only: one extra workgroup draws the NEXT round's indices
   // (pf_count draws into pf_out) while this kernel runs (0: none)
   Ctl* pf_ctl;

@@ -15,6 +15,10 @@ critical workgroup's phases sum exactly to the launch's in-kernel span (first
 workgroup start -> last wave end).  What rocprof adds beyond that span (the
 dispatch packet's begin -> first start, last end -> end of packet) is the
 rocprof average of the same run minus the span: `--rocprof-csv` reads it.
+
+The critic launch's row tiles run on twin workgroups (MDP_GRAD_TWIN=0 in the
+environment: one each); `critic_twins` lists per tile both twins' start, B5 exit
+and end, the B5 -> end span per half and the critic workgroups' start spread.
 """
 import argparse
 import csv
@@ -131,6 +135,45 @@ def launch_summary(b, roles):
     return out
 
 
+def wg_role(w, nwg, twin):
+    """workgroup index of the critic launch -> (row tile, half, role): nwg critic workgroups,
+    with twins their nwg second halves, nwg actor_pre workgroups, the draw"""
+    if w < twin * nwg:
+        return w % nwg, w // nwg, "critic_step"
+    if w < (twin + 1) * nwg:
+        return w - twin * nwg, 0, "actor_pre"
+    return 0, 0, "draw"
+
+
+def twin_table(b, nwg, twin):
+    """per row tile, each twin's start, B5 exit (point 28, its latest wave) and end, in us
+    from the launch's first workgroup start -- whether the split halved the tail (B5 -> end)
+    and what the longer dispatch ramp took back (first -> last critic workgroup start)"""
+    used = b[:, 64] > 0
+    t0 = int(b[used, 64].min())
+    tiles, tails, starts = [], [[] for _ in range(twin)], []
+    for t in range(nwg):
+        row = {"tile": t}
+        for h in range(twin):
+            w = h * nwg + t
+            assert wg_role(w, nwg, twin) == (t, h, "critic_step")
+            if not (b[w, 64] > 0 and b[w, 65] > b[w, 64] and b[w, 28] >= b[w, 62]):
+                continue
+            rs, re = int(b[w, 64]), int(b[w, 65])
+            k = (re - rs) * US / max(int(b[w, 63]) - int(b[w, 62]), 1)
+            b5 = (rs - t0) * US + (int(b[w, 28]) - int(b[w, 62])) * k
+            row[f"half{h}"] = {"wg": w, "start_us": round((rs - t0) * US, 3), "b5_us": round(b5, 3),
+                               "end_us": round((re - t0) * US, 3)}
+            tails[h].append((re - t0) * US - b5)
+            starts.append((rs - t0) * US)
+        tiles.append(row)
+    out = {"twin": twin, "critic_start_first_to_last_us": round(max(starts) - min(starts), 3), "tiles": tiles}
+    for h in range(twin):
+        out[f"b5_to_end_us_half{h}"] = {"median": round(float(np.median(tails[h])), 3),
+                                         "max": round(float(np.max(tails[h])), 3)}
+    return out
+
+
 def rocprof_avgs(path):
     avg = {}
     for r in csv.DictReader(open(path)):
@@ -206,21 +249,28 @@ def main():
     for _ in range(a.steps):
         r.step()
     r.synchronize()
-    buf = (ctypes.c_ulonglong * (2 * 160 * 72))()
+    WG = 256                                                         # MDP_BUD_WG (mdp_grads_r.hip)
+    buf = (ctypes.c_ulonglong * (2 * WG * 72))()
     assert fn(buf, 0) == 0
-    b = np.array(buf[:], dtype=np.uint64).reshape(2, 160, 72)
+    b = np.array(buf[:], dtype=np.uint64).reshape(2, WG, 72)
     nwg = 64
+    twin = 1 if os.environ.get("MDP_GRAD_TWIN", "1")[:1] == "0" else 2   # B = 1024: 193 workgroups <= 256 CUs
+    cw = twin * nwg
     res = {"config": "S2: simple_spread N=3, E=1024, B=1024, H=64; agent 1's launches of the last graph-replayed step",
            "rounds": r.rounds,
-           "critic": launch_summary(b[0], [("critic_step", range(nwg), CRITIC_STEP),
-                                            ("actor_pre", range(nwg, 2 * nwg), [(63, "last", "end")]),
-                                            ("draw", [2 * nwg], [(63, "last", "end")])]),
+           "critic": launch_summary(b[0], [("critic_step", range(nwg), CRITIC_STEP)]
+                                    + ([("critic_step_half1", range(nwg, cw), CRITIC_STEP)] if twin > 1 else [])
+                                    + [("actor_pre", range(cw, cw + nwg), [(63, "last", "end")]),
+                                       ("draw", [cw + nwg], [(63, "last", "end")])]),
+           "critic_twins": twin_table(b[0], nwg, twin),
            "actor": launch_summary(b[1], [("actor_step", range(nwg), ACTOR_STEP),
                                            ("critic_pre", range(nwg, 2 * nwg), CRITIC_PRE)])}
     s = json.dumps(res, indent=1)
     if a.out:
         open(a.out, "w").write(s)
-    print(s)
+        print(json.dumps({k: v for k, v in res["critic_twins"].items() if k != "tiles"}, indent=1))
+    else:
+        print(s)
 
 
 if __name__ == "__main__":

@@ -114,6 +114,10 @@ def parse_args(argv=None):
                         help="MADDPG with inferred policies: every agent learns approximators of the other agents' "
                              "policies from replay and builds its TD target from them (strict mode, one GPU, npz "
                              "checkpoints; not with --td3, --minimax or --prioritized-replay)")
+    parser.add_argument("--continuous-actions", action="store_true", default=False,
+                        help="Box action spaces: every agent that moves and does not speak gets a Box(2) space and a "
+                             "diagonal-Gaussian policy, its action the force itself (strict mode, one GPU; not with "
+                             "--prioritized-replay, --td3, --minimax or --approx-policies)")
     parser.add_argument("--approx-lambda", type=float, default=1e-3,
                         help="--approx-policies: weight of the approximators' entropy regulariser")
     # device-side policy evaluation (whole episodes in one launch; training state untouched)
@@ -403,10 +407,11 @@ def train(arglist):
     td3_flags(arglist, world)
     minimax_flags(arglist, world)
     approx_flags(arglist, world)
+    continuous_flags(arglist, world)
     try:
         runner = _make_runner(arglist, VecRunner, world, rank, per)
     except MdpError as e:      # e.g. prioritized replay with throughput mode or several GPUs
-        if not per and not arglist.td3 and not arglist.minimax and not arglist.approx_policies:
+        if not (per or arglist.td3 or arglist.minimax or arglist.approx_policies or arglist.continuous_actions):
             raise
         raise SystemExit(str(e))
     return _train(arglist, runner, exp_name, world, rank)
@@ -427,6 +432,21 @@ def td3_flags(arglist, world=1):
         raise SystemExit("--td3 runs on one GPU (--num-gpus 1)")
     if arglist.save_format == "tf1":
         raise SystemExit("--td3 saves npz checkpoints only (the second critic has no reference variable names)")
+
+
+def continuous_flags(arglist, world=1):
+    """--continuous-actions is Box spaces on one GPU in strict mode: refuse the
+    combinations the library has no variant for before anything is built"""
+    if not getattr(arglist, "continuous_actions", False):
+        return
+    for flag, on in (("--prioritized-replay", arglist.prioritized_replay), ("--td3", arglist.td3),
+                     ("--minimax", arglist.minimax), ("--approx-policies", arglist.approx_policies)):
+        if on:
+            raise SystemExit(f"--continuous-actions does not combine with {flag}")
+    if arglist.update_mode != "strict":
+        raise SystemExit("--continuous-actions needs --update-mode strict")
+    if (arglist.num_gpus or 1) > 1 or world > 1:
+        raise SystemExit("--continuous-actions runs on one GPU (--num-gpus 1)")
 
 
 def minimax_flags(arglist, world=1):
@@ -484,6 +504,7 @@ def _make_runner(arglist, VecRunner, world, rank, per):
                        capacity=arglist.buffer_size,
                        # the learning-curve windows of one terminal step span <= save_rate + E episodes
                        episode_log_rows=max(4096, 4 * arglist.num_envs, arglist.save_rate + 2 * arglist.num_envs),
+                       continuous=getattr(arglist, "continuous_actions", False),
                        **per, **td3_kwargs(arglist), **minimax_kwargs(arglist), **approx_kwargs(arglist))
     if arglist.update_mode != "strict":
         runner.eng.set_update_mode(arglist.update_mode)
@@ -601,6 +622,7 @@ def main(argv=None):
     td3_flags(arglist)
     minimax_flags(arglist)
     approx_flags(arglist)
+    continuous_flags(arglist)
     if arglist.num_gpus is not None:
         from maddpg_amd.launch import rank_launch_plan, run_ranks
         plan = rank_launch_plan(arglist.num_gpus, os.environ, os.path.abspath(__file__), argv,

@@ -150,6 +150,31 @@ int mdp_row_layout(const mdp_handle* h, int32_t agent, int32_t out6[6]);
 int mdp_set_act_dims(mdp_handle* h, const int32_t dims[MDP_MAX_AGENTS]);
 /* the widths in use (0 beyond n_agents) */
 int mdp_get_act_dims(const mdp_handle* h, int32_t dims[MDP_MAX_AGENTS]);
+/* Per-agent action spaces, kinds beside widths (make_pdtype, distributions.py:
+ * 408-422): agent i is Discrete(dims[i]), 1 <= dims[i] <= MDP_ACT_DIM, or
+ * Box(dims[i]), dims[i] in {1, 2}: a diagonal-Gaussian policy whose head is
+ * flat = [mean (d) | logstd (d)] and whose sample is a = mean + exp(logstd) * eps
+ * (distributions.py:343-371; no clamp on logstd).  eps is Box-Muller on the first
+ * two uniforms of the agent's [5] noise slot: r = sqrt(-2 ln(1 - u0)), eps_0 =
+ * r cos(2 pi u1), eps_1 = r sin(2 pi u1); u[2..4] are never read and every
+ * [.][MDP_ACT_DIM] array of this ABI keeps its shape.  No device layout changes:
+ * the head fills the first 2 d columns of the W3 / b3 block, the action the first d
+ * entries of its slot, and everything beyond is exactly 0, as for a narrow Discrete
+ * agent.  Logical shapes: actor W3 [num_units, 2 d], b3 [2 d]; a critic W1 counts d
+ * rows for the agent's action.  mdp_actor_logits returns flat; MDP_EVAL_MEAN plays
+ * the mean.  On a handle with a device scenario an agent keeps the scenario's own
+ * Discrete space or, if it moves and does not speak, becomes Box(2), whose action is
+ * the force (a[0], a[1]) * accel, unclipped; anything else is refused.
+ * A handle with a Box agent trains in strict mode on one GPU, on the general
+ * gradient kernels (mdp_grad_variant 0); prioritized replay, MATD3, M3DDPG,
+ * inferred policies, throughput mode and data parallelism refuse it with a message.
+ * Accepted when mdp_set_act_dims is (and before any of the enables above).  < 0
+ * with a message for an unknown kind or a width outside the kind's range. */
+#define MDP_ACT_DISCRETE 0
+#define MDP_ACT_BOX 1
+int mdp_set_act_spaces(mdp_handle* h, const int32_t kinds[MDP_MAX_AGENTS], const int32_t dims[MDP_MAX_AGENTS]);
+/* the kinds and widths in use (0 beyond n_agents); either pointer may be NULL */
+int mdp_get_act_spaces(const mdp_handle* h, int32_t kinds[MDP_MAX_AGENTS], int32_t dims[MDP_MAX_AGENTS]);
 
 /* ---- parameters (golden injection, checkpoint; tf_util.py:259-273) --- */
 int mdp_set_params(mdp_handle* h, int32_t agent, int32_t which, const float* src_host, int64_t n);

@@ -19,6 +19,7 @@ LIB_PATH = os.environ.get("MDP_LIB") or os.path.join(HERE, "libmaddpg_hip.so")
 HEADER = os.path.join(os.path.dirname(HERE), "include", "maddpg_hip.h")
 
 MAX_AGENTS = 8
+ACT_DISCRETE, ACT_BOX = 0, 1   # MDP_ACT_DISCRETE / MDP_ACT_BOX (mdp_set_act_spaces)
 ACT_DIM = 5   # MDP_ACT_DIM: the widest action space, and the width of every device action slot
 BENCH_W = 8   # MDP_BENCH_W: floats per agent benchmark_data record
 MAX_UNITS = 256  # MDP_MAX_UNITS: largest --num-units
@@ -104,6 +105,8 @@ SIGNATURES = {
     "mdp_row_layout": (ctypes.c_int, [_P, _I32, _I32P]),
     "mdp_set_act_dims": (ctypes.c_int, [_P, _I32P]),
     "mdp_get_act_dims": (ctypes.c_int, [_P, _I32P]),
+    "mdp_set_act_spaces": (ctypes.c_int, [_P, _I32P, _I32P]),
+    "mdp_get_act_spaces": (ctypes.c_int, [_P, _I32P, _I32P]),
     "mdp_set_params": (ctypes.c_int, [_P, _I32, _I32, _F32P, _I64]),
     "mdp_get_params": (ctypes.c_int, [_P, _I32, _I32, _F32P, _I64]),
     "mdp_get_beta_powers": (ctypes.c_int, [_P, _I32, _I32, _F32P]),

@@ -332,6 +332,7 @@ struct mdp_handle {
   // MDP_GENERAL_GRADS=1 in the environment at create: always use the general
   // grad kernels (mdp_grads.hip) -- lets tests compare both paths
   bool general_grads = false;
+  bool box = false;  // some agent has a Box space (mdp_set_act_spaces; grads_r_ok then refuses the register kernels)
   // single-GPU optimizer step as one k_reduce_apply launch (MDP_UNFUSED_APPLY=1: k_reduce + k_apply)
   bool fused_apply = true;
   // ... with the reduced gradient kept in registers where mdp_ra_lanes allows
@@ -644,7 +645,7 @@ const NDesc& net_of(mdp_handle* h, int agent, int net) {
 // logical (TF variable) shape of tensor t of agent's net (0 actor, 1 critic),
 // whose device block is padded in the hidden width and in the action slots:
 // (W1 [in, u], b1 [u], W2 [u, u], b2 [u], W3 [u, out], b3 [out], u = --num-units;
-// the actor's out is the agent's action width A_i, the critic's in counts A_j
+// the actor's out is the agent's head width -- A_i, or 2 d_i for Box(d_i) -- the critic's in counts the action width A_j / d_j
 // per action slot: sum_obs + sum_j A_j, or obs_i + A_i for a DDPG critic)
 void logical_shape(const mdp_handle* h, int agent, int net, int t, int* rows, int* cols) {
   const Topo& T = h->L.topo;
@@ -653,7 +654,7 @@ void logical_shape(const mdp_handle* h, int agent, int net, int t, int* rows, in
   const int u = h->L.H_log;
   *rows = (t == 2 || t == 4) ? u : d.t[t].rows;
   *cols = t < 4 ? u : d.t[t].cols;
-  if (!net && t >= 4) *cols = topo_act_w(T, agent);
+  if (!net && t >= 4) *cols = topo_head_w(T, agent);  // Box(d): mean | logstd
   if (net && t == 0) {
     int pad = MDP_ACT_DIM - topo_act_w(T, agent);
     if (!ag.local_q) {
@@ -991,7 +992,7 @@ OptNet opt_own(mdp_handle* h, int agent, int net) {
   o.part = h->ra_part;
   o.slot = o.net_id;
   o.polyak = net ? 0 : 1;
-  o.stats_mode = net ? 1 : 1 + topo_act_w(h->L.topo, agent);
+  o.stats_mode = net ? 1 : 1 + topo_head_w(h->L.topo, agent);
   o.bump_ctr = net ? 0 : 1;
   o.own = true;
   return o;
@@ -1842,6 +1843,9 @@ int per_update(mdp_handle* h, int agent0, int agents, int count, const int32_t* 
 }
 
 const char* kPerNoDp = "prioritized replay runs on one GPU in strict mode: no data-parallel exchange";
+const char* kBoxOnly =
+    "a handle with a Box action space (mdp_set_act_spaces) trains in strict mode on one GPU: no prioritized replay, "
+    "MATD3, M3DDPG, inferred policies, throughput mode or data parallelism";
 const char* kTd3NoDp = "MATD3 (mdp_td3_enable) runs on one GPU in strict mode: no data-parallel exchange";
 const char* kMmNoDp = "M3DDPG (mdp_minimax_enable) runs on one GPU in strict mode: no data-parallel exchange";
 
@@ -2178,11 +2182,73 @@ int mdp_set_act_dims(mdp_handle* h, const int32_t dims[MDP_MAX_AGENTS]) {
   const int n = h->cfg.n_agents;
   for (int i = 0; i < n; ++i)
     if (dims[i] < 1 || dims[i] > MDP_ACT_DIM) return fail(h, "mdp_set_act_dims: every width must be in 1..5");
-  if (h->cfg.scenario != MDP_SCN_NONE)
+  if (h->cfg.scenario != MDP_SCN_NONE) {
+    EnvDesc e;  // (the scenario's own widths: the handle's may be a Box's by now)
+    std::vector<int> od, widths;
+    std::string err;
+    if (!make_env(h->cfg, e, od, widths, err)) return fail(h, err.c_str());
     for (int i = 0; i < n; ++i)
-      if (dims[i] != topo_act_w(h->L.topo, i))
+      if (dims[i] != widths[i])
         return fail(h, "mdp_set_act_dims: widths differ from the scenario's own (a scenario handle needs no call)");
-  for (int i = 0; i < n; ++i) topo_set_act_w(h->L.topo, i, dims[i]);
+  }
+  for (int i = 0; i < n; ++i) topo_set_act_w(h->L.topo, i, dims[i]);  // (every kind Discrete)
+  h->box = false;
+  return 0;
+}
+
+// kinds beside widths.  A handle with a Box agent runs the general gradient
+// kernels at every H (grads_r_ok: the register kernels know the Gumbel-softmax
+// only), as MATD3's does.
+int mdp_set_act_spaces(mdp_handle* h, const int32_t kinds[MDP_MAX_AGENTS], const int32_t dims[MDP_MAX_AGENTS]) {
+  MDP_NEED(h);
+  if (!kinds || !dims) return fail(h, "mdp_set_act_spaces: kinds or dims is null");
+  if (h->started || h->trained)
+    return fail(h, "mdp_set_act_spaces: call it before the handle's first parameter write, act, update or env call");
+  const int n = h->cfg.n_agents;
+  bool box = false;
+  for (int i = 0; i < n; ++i) {
+    if (kinds[i] == MDP_ACT_BOX) {
+      if (dims[i] < 1 || dims[i] > 2) return fail(h, "mdp_set_act_spaces: a Box space must have 1 or 2 dimensions");
+      box = true;
+    } else if (kinds[i] == MDP_ACT_DISCRETE) {
+      if (dims[i] < 1 || dims[i] > MDP_ACT_DIM) return fail(h, "mdp_set_act_spaces: every Discrete width must be in 1..5");
+    } else {
+      return fail(h, "mdp_set_act_spaces: unknown kind (MDP_ACT_DISCRETE, MDP_ACT_BOX)");
+    }
+  }
+  if (h->cfg.scenario != MDP_SCN_NONE) {
+    EnvDesc e;
+    std::vector<int> od, widths;
+    std::string err;
+    if (!make_env(h->cfg, e, od, widths, err)) return fail(h, err.c_str());
+    for (int i = 0; i < n; ++i) {
+      if (kinds[i] == MDP_ACT_DISCRETE) {
+        if (dims[i] != widths[i])
+          return fail(h, "mdp_set_act_spaces: a Discrete width differs from the scenario's own");
+      } else if (dims[i] != 2 || !e.movable[i] || !env_silent(h->cfg.scenario, i)) {
+        return fail(h, "mdp_set_act_spaces: on a scenario handle only an agent that moves and does not speak may be "
+                       "Box, and Box(2) only (its action is the force)");
+      }
+    }
+  }
+  if (box) {
+    if (h->per || h->td3 || h->minimax || h->approx)
+      return fail(h, (std::string("mdp_set_act_spaces: ") + kBoxOnly).c_str());
+    if (h->update_mode != 0 || h->comm || h->xbuf || h->p2p)
+      return fail(h, (std::string("mdp_set_act_spaces: ") + kBoxOnly).c_str());
+  }
+  for (int i = 0; i < n; ++i) topo_set_act_space(h->L.topo, i, kinds[i] == MDP_ACT_BOX, dims[i]);
+  h->box = box;
+  return 0;
+}
+
+int mdp_get_act_spaces(const mdp_handle* h, int32_t kinds[MDP_MAX_AGENTS], int32_t dims[MDP_MAX_AGENTS]) {
+  if (unusable(h)) return -1;
+  for (int i = 0; i < MDP_MAX_AGENTS; ++i) {
+    const bool in = i < h->cfg.n_agents;
+    if (kinds) kinds[i] = in && topo_act_box(h->L.topo, i) ? MDP_ACT_BOX : MDP_ACT_DISCRETE;
+    if (dims) dims[i] = in ? topo_act_w(h->L.topo, i) : 0;
+  }
   return 0;
 }
 
@@ -2361,7 +2427,7 @@ int mdp_act(mdp_handle* h, int32_t agent, int32_t target, const float* obs_dev, 
   a.x = obs_dev;
   a.out = act_dev;
   a.gumbel = 1;
-  a.act_w = topo_act_w(h->L.topo, agent);
+  a.act_w = (int)topo_act_space(h->L.topo, agent);
   a.u = u_dev;
   a.seed = h->cfg.seed;
   a.stream = 0x40000u | (uint32_t)(agent << 1) | (uint32_t)(target ? 1 : 0);
@@ -2634,6 +2700,7 @@ int mdp_dp_unique_id(uint8_t* out128) {
 
 int mdp_dp_init(mdp_handle* h, const uint8_t* id128, int32_t world, int32_t rank) {
   if (unusable(h) || !id128) return -1;
+  if (h->box) return fail(h, (std::string("mdp_dp_init: ") + kBoxOnly).c_str());
   if (h->per) return fail(h, kPerNoDp);
   if (h->td3) return fail(h, (std::string("mdp_dp_init: ") + kTd3NoDp).c_str());
   if (h->minimax) return fail(h, (std::string("mdp_dp_init: ") + kMmNoDp).c_str());
@@ -2663,6 +2730,7 @@ int mdp_dp_init(mdp_handle* h, const uint8_t* id128, int32_t world, int32_t rank
 
 int mdp_dp_xgmi_open(mdp_handle* h, int32_t world, int32_t rank, uint8_t* handle_out) {
   if (unusable(h) || !handle_out) return -1;
+  if (h->box) return fail(h, (std::string("mdp_dp_xgmi_open: ") + kBoxOnly).c_str());
   if (h->per) return fail(h, kPerNoDp);
   if (h->td3) return fail(h, (std::string("mdp_dp_xgmi_open: ") + kTd3NoDp).c_str());
   if (h->minimax) return fail(h, (std::string("mdp_dp_xgmi_open: ") + kMmNoDp).c_str());
@@ -2696,6 +2764,7 @@ int mdp_dp_xgmi_open(mdp_handle* h, int32_t world, int32_t rank, uint8_t* handle
 
 int mdp_dp_xgmi_connect(mdp_handle* h, const uint8_t* handles) {
   if (unusable(h) || !handles) return -1;
+  if (h->box) return fail(h, (std::string("mdp_dp_xgmi_connect: ") + kBoxOnly).c_str());
   if (!h->xbuf) return fail(h, "mdp_dp_xgmi_connect: call mdp_dp_xgmi_open first");
   if (!h->x_opened.empty()) return fail(h, "mdp_dp_xgmi_connect: already connected");
   const int W = h->x_world, r = h->x_rank;
@@ -2723,6 +2792,7 @@ int mdp_dp_xgmi_connect(mdp_handle* h, const uint8_t* handles) {
 
 int mdp_dp_xgmi_probe(mdp_handle* h, int32_t* mismatches) {
   if (unusable(h)) return -1;
+  if (h->box) return fail(h, (std::string("mdp_dp_xgmi_probe: ") + kBoxOnly).c_str());
   if (!h->xd_dev) return fail(h, "mdp_dp_xgmi_probe: not connected");
   const int nchunk = MDP_XCH_PROBE / 256;
   HIPCHK(h, hipMemsetAsync(h->x_probe, 0, 2 * sizeof(uint32_t), h->stream));
@@ -2739,6 +2809,7 @@ int mdp_dp_xgmi_probe(mdp_handle* h, int32_t* mismatches) {
 
 int mdp_dp_xgmi_enable(mdp_handle* h) {
   if (unusable(h)) return -1;
+  if (h->box) return fail(h, (std::string("mdp_dp_xgmi_enable: ") + kBoxOnly).c_str());
   // (an approx handle never gets past mdp_dp_xgmi_open, so say why before "not connected")
   if (h->approx) return fail(h, (std::string("mdp_dp_xgmi_enable: ") + kApxNoDp).c_str());
   if (!h->xd_dev) return fail(h, "mdp_dp_xgmi_enable: not connected");
@@ -2815,6 +2886,7 @@ int mdp_set_update_mode(mdp_handle* h, int32_t mode) {
   if (unusable(h)) return -1;
   if (mode != 0 && mode != 1) return fail(h, "update mode must be 0 (strict) or 1 (throughput)");
   if (mode == 1) {
+    if (h->box) return fail(h, (std::string("mdp_set_update_mode: ") + kBoxOnly).c_str());
     if (h->td3) return fail(h, "mdp_set_update_mode: mode 1 (throughput) is not supported with MATD3 (mdp_td3_enable)");
     if (h->minimax)
       return fail(h, "mdp_set_update_mode: mode 1 (throughput) is not supported with M3DDPG (mdp_minimax_enable)");
@@ -2836,6 +2908,7 @@ int mdp_set_update_mode(mdp_handle* h, int32_t mode) {
 
 int mdp_update_all(mdp_handle* h, const int32_t* idx_dev, const float* u_tgt_dev, const float* u_act_dev) {
   if (unusable(h)) return -1;
+  if (h->box) return fail(h, (std::string("mdp_update_all: ") + kBoxOnly).c_str());
   if (h->td3) return fail(h, "mdp_update_all: throughput mode is not supported with MATD3 (mdp_td3_enable)");
   if (h->minimax) return fail(h, "mdp_update_all: throughput mode is not supported with M3DDPG (mdp_minimax_enable)");
   if (h->approx)
@@ -3595,6 +3668,7 @@ int64_t mdp_per_bytes(const mdp_config* cfg) {
 int mdp_per_enable(mdp_handle* h, void* buf_dev, int64_t bytes, float alpha, float beta0, float beta_inc, float eps,
                    float abs_err_upper) {
   MDP_NEED(h);
+  if (h->box) return fail(h, (std::string("mdp_per_enable: ") + kBoxOnly).c_str());
   if (h->per) return fail(h, "mdp_per_enable: already enabled");
   if (h->td3) return fail(h, "mdp_per_enable: prioritized replay and MATD3 (mdp_td3_enable) do not combine");
   if (h->minimax) return fail(h, "mdp_per_enable: prioritized replay and M3DDPG (mdp_minimax_enable) do not combine");
@@ -3655,6 +3729,7 @@ int64_t mdp_td3_bytes(const mdp_config* cfg) {
 
 int mdp_td3_enable(mdp_handle* h, void* buf_dev, int64_t bytes, int32_t policy_delay) {
   MDP_NEED(h);
+  if (h->box) return fail(h, (std::string("mdp_td3_enable: ") + kBoxOnly).c_str());
   if (h->td3) return fail(h, "mdp_td3_enable: already enabled");
   if (h->trained) return fail(h, "mdp_td3_enable: call it before the handle's first update, round or train call");
   if (policy_delay < 1 || policy_delay > 8) return fail(h, "mdp_td3_enable: policy_delay must be in 1..8");
@@ -3720,6 +3795,7 @@ int mdp_td3_info(mdp_handle* h, int32_t agent, double out4[4]) {
 // ----------------------------------------------------------------- M3DDPG
 int mdp_minimax_enable(mdp_handle* h, const float* eps_host) {
   MDP_NEED(h);
+  if (h->box) return fail(h, (std::string("mdp_minimax_enable: ") + kBoxOnly).c_str());
   if (h->minimax) return fail(h, "mdp_minimax_enable: already enabled");
   if (h->trained)
     return fail(h, "mdp_minimax_enable: call it before the handle's first update, round or train call");
@@ -3787,6 +3863,7 @@ int64_t mdp_approx_bytes(const mdp_config* cfg) {
 
 int mdp_approx_enable(mdp_handle* h, void* buf_dev, int64_t bytes, float lambda) {
   MDP_NEED(h);
+  if (h->box) return fail(h, (std::string("mdp_approx_enable: ") + kBoxOnly).c_str());
   if (h->approx) return fail(h, "mdp_approx_enable: already enabled");
   if (h->trained)
     return fail(h, "mdp_approx_enable: call it before the handle's first update, round or train call");

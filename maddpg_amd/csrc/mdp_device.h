@@ -518,6 +518,80 @@ __device__ __forceinline__ void gumbel_softmax(const float* logits, const float*
   gumbel_softmax_pre(logits, gn, a, A);
 }
 
+// An agent whose action space is Box(d), d in {1, 2} (topo_act_box): the head
+// is flat = [mean (d) | logstd (d)] in the first 2 d columns of the 5-wide
+// block, the sample a = mean + exp(logstd) * eps (distributions.py:343-371;
+// no clamp on logstd, the reference has none).  eps: Box-Muller on the slot's
+// first two uniforms; 1 - u0 is in (0, 1] (u01 is in [0, 1)), so r is finite,
+// at most ~5.65.  u[2..4] are never read.  The precise libm forms throughout
+// (sincospif reduces 2 u1 exactly): none of this is on the register kernels'
+// path, and the sampled action is compared at a tolerance set by the fp32
+// restatement's own error.  Products and sums are rounded one by one (no fma
+// contraction), so the restatement's operation order is the device's.
+__device__ __forceinline__ void gauss_noise2(const float* u, float* eps) {
+  const float r = sqrtf(__fmul_rn(-2.0f, logf(__fsub_rn(1.0f, u[0]))));
+  float s, c;
+  sincospif(__fmul_rn(2.0f, u[1]), &s, &c);
+  eps[0] = __fmul_rn(r, c);
+  eps[1] = __fmul_rn(r, s);
+}
+// forward: the d action entries, exactly 0.0f in the rest of the slot; se (or
+// null) receives std_k * eps_k, the backward's dlogstd factor, in se[0..d)
+__device__ __forceinline__ void gauss_sample_pre(const float* flat, const float* eps, float* a, int d, float* se) {
+#pragma unroll
+  for (int k = 0; k < MDP_ACT_DIM; ++k) a[k] = 0.f;
+#pragma unroll
+  for (int k = 0; k < 2; ++k) {
+    if (k < d) {
+      const float s = __fmul_rn(expf(flat[d + k]), eps[k]);
+      a[k] = __fadd_rn(flat[k], s);
+      if (se) se[k] = s;
+    }
+  }
+}
+// backward through the sample + the regulariser on every head entry:
+// dmean_k = da_k, dlogstd_k = da_k * std_k * eps_k, + flat * 2 reg / (B 2d);
+// columns >= 2 d exactly 0
+__device__ __forceinline__ void gauss_backward(const float* flat, const float* da, const float* se, int d,
+                                               float reg_scale, float* dflat) {
+#pragma unroll
+  for (int k = 0; k < MDP_ACT_DIM; ++k) {  // (static indices into dflat: it may live in registers)
+    const int j = min(k < d ? k : k - d, 1);
+    const float g = k < d ? da[j] : __fmul_rn(da[j], se[j]);
+    dflat[k] = k < 2 * d ? __fadd_rn(g, __fmul_rn(flat[k], reg_scale)) : 0.f;
+  }
+}
+// The one sampler of every call site: sp is the agent's nibble of Topo::act_w4
+// (topo_act_space: kind bit | action width).  The Box form is laid out behind
+// the hot code; mean: the distribution's mode (noise-free softmax / the mean).
+__device__ __forceinline__ void policy_sample_pre(const float* head, const float* u, bool mean, float* a, uint32_t sp,
+                                                  float* se = nullptr) {
+  if (__builtin_expect((sp & 8u) != 0u, 0)) {
+    const int d = (int)(sp & 7u);
+    if (mean) {  // mode() is the mean itself (an infinite std must not meet a zero eps)
+#pragma unroll
+      for (int k = 0; k < MDP_ACT_DIM; ++k) a[k] = k < d ? head[k] : 0.f;
+      return;
+    }
+    float eps[2];
+    gauss_noise2(u, eps);
+    gauss_sample_pre(head, eps, a, d, se);
+    return;
+  }
+  float gn[MDP_ACT_DIM];
+  if (mean) {
+#pragma unroll
+    for (int k = 0; k < MDP_ACT_DIM; ++k) gn[k] = 0.f;
+  } else {
+    gumbel_noise5(u, gn);
+  }
+  gumbel_softmax_pre(head, gn, a, (int)(sp & 7u));
+}
+__device__ __forceinline__ void policy_sample(const float* head, const float* u, float* a, uint32_t sp,
+                                              float* se = nullptr) {
+  policy_sample_pre(head, u, false, a, sp, se);
+}
+
 // ------------------------------------------------------ phase-parallel tiles
 // (k_critic_grad / k_actor_grad, 512-thread workgroups)  A "job" is one dense
 // layer Y[16][N] = act(X[16][K] @ W[K][N] + b) of one net; all jobs of a

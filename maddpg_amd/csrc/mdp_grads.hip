@@ -666,7 +666,7 @@ __device__ __forceinline__ void critic_body(const A& a, const Topo& T, const int
       } else {
         uniforms5(a.seed, (uint32_t)((a.agent << 8) | (j + 1)), ctr, (uint32_t)(r0 + row), u);
       }
-      gumbel_softmax(lg + jb * MDP_R * 8 + row * 8, u, act, topo_act_w(T, j));
+      policy_sample(lg + jb * MDP_R * 8 + row * 8, u, act, topo_act_space(T, j));
       const int dst = lq ? ag.obs_dim : T.sum_obs + MDP_ACT_DIM * j;
       for (int k = 0; k < MDP_ACT_DIM; ++k) xt[row * ldc + dst + k] = act[k];
     }
@@ -958,7 +958,8 @@ __device__ __forceinline__ void actor_body(const AA& a, const Topo& T, const int
       } else {
         uniforms5(a.seed, (uint32_t)((a.agent << 8) | 0x80), ctr, (uint32_t)(r0 + lane), u);
       }
-      gumbel_softmax(lg + lane * 8, u, av + lane * 8, topo_act_w(T, a.agent));
+      // (a Box agent: std * eps, the backward's factor, behind the slot's 5 entries)
+      policy_sample(lg + lane * 8, u, av + lane * 8, topo_act_space(T, a.agent), av + lane * 8 + MDP_ACT_DIM);
       if (!par)
         for (int k = 0; k < MDP_ACT_DIM; ++k) x[lane * ldc + ag.a_in_off + k] = av[lane * 8 + k];
     }
@@ -1102,13 +1103,19 @@ __device__ __forceinline__ void actor_body(const AA& a, const Topo& T, const int
     // softmax backward + regulariser: dlogits = (da - sum(a*da)) * a + reg*2*p/(B*A); loss partials
     double s_q = 0.0, s_p = 0.0;
     if (lane < MDP_R) {
-      const int aw = topo_act_w(T, a.agent);
+      const int aw = topo_head_w(T, a.agent);
       const float reg_scale = __builtin_expect(aw == MDP_ACT_DIM, 1) ? a.reg_scale : T.reg_scale_w[aw - 1];
-      float dot = 0.f;
-      for (int k = 0; k < MDP_ACT_DIM; ++k) dot += da[lane * 8 + k] * av[lane * 8 + k];
-      for (int k = 0; k < MDP_ACT_DIM; ++k) {
-        const float g = (da[lane * 8 + k] - dot) * av[lane * 8 + k] + lg[lane * 8 + k] * reg_scale;
-        dl[lane * 8 + k] = lane < nvalid ? g : 0.f;
+      if (__builtin_expect(topo_act_box(T, a.agent), 0)) {  // Gaussian head: dmean | dlogstd
+        float g[MDP_ACT_DIM];
+        gauss_backward(lg + lane * 8, da + lane * 8, av + lane * 8 + MDP_ACT_DIM, aw >> 1, reg_scale, g);
+        for (int k = 0; k < MDP_ACT_DIM; ++k) dl[lane * 8 + k] = lane < nvalid ? g[k] : 0.f;
+      } else {
+        float dot = 0.f;
+        for (int k = 0; k < MDP_ACT_DIM; ++k) dot += da[lane * 8 + k] * av[lane * 8 + k];
+        for (int k = 0; k < MDP_ACT_DIM; ++k) {
+          const float g = (da[lane * 8 + k] - dot) * av[lane * 8 + k] + lg[lane * 8 + k] * reg_scale;
+          dl[lane * 8 + k] = lane < nvalid ? g : 0.f;
+        }
       }
       if (lane < nvalid) {
         s_q = (double)qv[lane * 8];

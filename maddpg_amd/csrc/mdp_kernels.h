@@ -452,7 +452,7 @@ struct EvalArgs {
   const float* u;
   uint64_t seed;
   uint32_t stream, ctr;
-  int act_w;  // gumbel: the agent's action width (topo_act_w)
+  int act_w;  // gumbel: the agent's action space, kind bit | action width (topo_act_space)
 };
 
 // kernel width that serves --num-units u: the gradient / rollout / eval kernels
@@ -525,9 +525,10 @@ inline int lds_critic_pre_bytes(const Topo& t) {
   return 4 * words;
 }
 // the fast kernels hold every weight of a wave in registers: H = 64, at most 3
-// target actors, actor inputs <= 64, critic inputs <= 80, target-critic action part <= 20
+// target actors, actor inputs <= 64, critic inputs <= 80, target-critic action part <= 20;
+// their sampler is the Gumbel-softmax: no agent of the topology may have a Box space
 inline bool grads_r_ok(const Topo& t, int agent) {
-  if (t.H != 64) return false;
+  if (t.H != 64 || topo_any_box(t)) return false;
   const ADesc& ag = t.ag[agent];
   const int na = ag.local_q ? 1 : t.n;
   if (na > 3) return false;

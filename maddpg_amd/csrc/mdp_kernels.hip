@@ -652,17 +652,22 @@ __device__ inline void env_bench(const EnvDesc& E, const float* p, int goal, flo
 // tile's [R][2 MDP_MAX_ENT] state; f: [R][3 MDP_MAX_ENT] force scratch; act:
 // row r's actions at act + r * ldr.  Every thread of the workgroup calls it.
 __device__ inline void env_physics_tile(const EnvDesc& E, float* sp, float* sv, const float* act, int ldr, float* f,
-                                        int nvalid) {
+                                        int nvalid, uint32_t act_w4) {
   const int n = E.n_agents, ne = E.n_agents + E.n_landmarks;
   const float k = 1e-3f;  // contact_margin
   for (int q = threadIdx.x; q < nvalid * ne; q += MDP_NT) {
     const int r = q / ne, e = q - r * ne;
     const float* p = sp + r * 2 * MDP_MAX_ENT;
     float fx = 0.f, fy = 0.f, has = 0.f;
-    if (e < n) {  // environment._set_action, discrete action space
+    if (e < n) {  // environment._set_action
       const float* a = act + r * ldr + e * MDP_ACT_DIM;
-      fx = (a[1] - a[2]) * E.accel[e];
-      fy = (a[3] - a[4]) * E.accel[e];
+      if (__builtin_expect(((act_w4 >> (4 * e)) & 8u) != 0u, 0)) {  // Box(2): the force itself, unclipped
+        fx = a[0] * E.accel[e];
+        fy = a[1] * E.accel[e];
+      } else {  // discrete action space
+        fx = (a[1] - a[2]) * E.accel[e];
+        fy = (a[3] - a[4]) * E.accel[e];
+      }
       has = 1.f;
     }
     if (E.collide[e] && E.movable[e]) {
@@ -975,7 +980,7 @@ __global__ __launch_bounds__(MDP_NT) void k_rollout(RolloutArgs a) {
           }
         }
         wave_sync();
-        if (lane < MDP_R) gumbel_softmax(lgj + lane * 8, u, rowt + lane * ldr + aj.act_off, topo_act_w(T, j));
+        if (lane < MDP_R) policy_sample(lgj + lane * 8, u, rowt + lane * ldr + aj.act_off, topo_act_space(T, j));
       }
       __syncthreads();
       MDP_STAMP(42);
@@ -1008,7 +1013,7 @@ __global__ __launch_bounds__(MDP_NT) void k_rollout(RolloutArgs a) {
         } else {
           uniforms5(a.seed, 0x10000u | (uint32_t)j, step_s(), (uint32_t)(a.env_base + e0 + tid), u);
         }
-        gumbel_softmax(lg + tid * 8, u, dst, topo_act_w(T, j));
+        policy_sample(lg + tid * 8, u, dst, topo_act_space(T, j));
       }
     }
     __syncthreads();
@@ -1018,7 +1023,7 @@ __global__ __launch_bounds__(MDP_NT) void k_rollout(RolloutArgs a) {
   // physics (one thread per (env, entity)), then rewards and bookkeeping (one
   // thread per env, wave 0) beside the next observations (one thread per
   // (env, agent), the other waves); terminal envs reset after both
-  env_physics_tile(E, sp, sv, rowt + T.ag[0].act_off, ldr, sfo, nvalid);
+  env_physics_tile(E, sp, sv, rowt + T.ag[0].act_off, ldr, sfo, nvalid, T.act_w4);
   bool term = false;
   if (tid < nvalid) {
     const float* p = sp + tid * 2 * MDP_MAX_ENT;
@@ -1219,21 +1224,16 @@ __global__ __launch_bounds__(MDP_NT) void k_eval_episodes(Args a) {
   for (int t = 0; t < nst; ++t) {
     // the sample of (row lane, agent j): k_rollout's, or the noise-free softmax
     auto sample = [&](const float* logits, int row, int j, float* dst) {
-      float gn[MDP_ACT_DIM];
-      if (mean) {
-#pragma unroll
-        for (int k = 0; k < MDP_ACT_DIM; ++k) gn[k] = 0.f;
-      } else {
-        float u[MDP_ACT_DIM];
+      float u[MDP_ACT_DIM];
+      if (!mean) {
         if (a.u_in) {
           for (int k = 0; k < MDP_ACT_DIM; ++k)
             u[k] = row < nvalid ? a.u_in[(((int64_t)(i0 + row) * nst + t) * n + j) * MDP_ACT_DIM + k] : 0.5f;
         } else {
           uniforms5(a.seed, 0x70000u | (uint32_t)j, (uint32_t)t, a.first + (uint32_t)(i0 + row), u);
         }
-        gumbel_noise5(u, gn);
       }
-      gumbel_softmax_pre(logits, gn, dst, topo_act_w(T, j));
+      policy_sample_pre(logits, u, mean, dst, topo_act_space(T, j));
     };
     // observations, one thread per (episode, agent); the listener hears the
     // speaker's action of the previous step (state.c; zero in the first)
@@ -1319,7 +1319,7 @@ __global__ __launch_bounds__(MDP_NT) void k_eval_episodes(Args a) {
       }
     }
 
-    env_physics_tile(E, sp, sv, rowt + T.ag[0].act_off, ldr, sfo, nvalid);
+    env_physics_tile(E, sp, sv, rowt + T.ag[0].act_off, ldr, sfo, nvalid, T.act_w4);
     if (tid < nvalid) {
       const float* p = sp + tid * 2 * MDP_MAX_ENT;
       float* rew = rowt + tid * ldr + T.ag[0].rew_off;  // rew_0 .. rew_{n-1} are contiguous (mdp_topo.h)
@@ -1443,7 +1443,7 @@ __global__ __launch_bounds__(MDP_NT) void k_mlp_eval(EvalArgs a) {
       } else {
         uniforms5(a.seed, a.stream, a.ctr, (uint32_t)row, u);
       }
-      gumbel_softmax(lg + tid * 8, u, act, a.act_w);
+      policy_sample(lg + tid * 8, u, act, (uint32_t)a.act_w);
       for (int k = 0; k < MDP_ACT_DIM; ++k) a.out[(int64_t)row * MDP_ACT_DIM + k] = act[k];
     } else {
       for (int k = 0; k < a.net.out; ++k) a.out[(int64_t)row * a.net.out + k] = lg[tid * 8 + k];

@@ -41,6 +41,11 @@ struct Topo {
   // pad entries are exactly zero everywhere.  (Behind the descriptors, in one
   // word: the argument blocks of the gradient kernels end with their Topo, so
   // every field the all-5 path reads stays where it was.)
+  // Bit 3 of agent j's nibble is its action kind (mdp_set_act_spaces): 0
+  // Discrete(A_j), the low bits A_j; 1 Box(d_j), the low bits d_j in {1, 2}.
+  // A Box actor's head is [mean (d) | logstd (d)], 2 d <= MDP_ACT_DIM wide in
+  // the same W3 / b3 block; its action fills the first d entries of the slot
+  // (topo_act_w is the ACTION width of either kind, topo_head_w the head's).
   uint32_t act_w4;
   float reg_scale_w[MDP_ACT_DIM];  // actor regulariser 2 * actor_reg / (B * A) for A = 1..5 (A < 5: ActorArgs::reg_scale is A = 5's)
 };
@@ -48,8 +53,28 @@ struct Topo {
 __host__ __device__
 #endif
 inline int topo_act_w(const Topo& t, int j) { return (int)((t.act_w4 >> (4 * j)) & 7u); }
-inline void topo_set_act_w(Topo& t, int j, int w) {
-  t.act_w4 = (t.act_w4 & ~(7u << (4 * j))) | ((uint32_t)w << (4 * j));
+// agent j's whole nibble: kind bit | action width (the samplers' argument)
+#if defined(__HIPCC__)
+__host__ __device__
+#endif
+inline uint32_t topo_act_space(const Topo& t, int j) { return (t.act_w4 >> (4 * j)) & 15u; }
+#if defined(__HIPCC__)
+__host__ __device__
+#endif
+inline bool topo_act_box(const Topo& t, int j) { return ((t.act_w4 >> (4 * j)) & 8u) != 0u; }
+// width of the actor's head: A_j logits, or mean | logstd of a Box(d_j)
+#if defined(__HIPCC__)
+__host__ __device__
+#endif
+inline int topo_head_w(const Topo& t, int j) { return topo_act_w(t, j) << (topo_act_box(t, j) ? 1 : 0); }
+inline void topo_set_act_space(Topo& t, int j, bool box, int w) {
+  t.act_w4 = (t.act_w4 & ~(15u << (4 * j))) | (((uint32_t)w | (box ? 8u : 0u)) << (4 * j));
+}
+inline void topo_set_act_w(Topo& t, int j, int w) { topo_set_act_space(t, j, false, w); }
+inline bool topo_any_box(const Topo& t) {
+  for (int j = 0; j < t.n; ++j)
+    if (topo_act_box(t, j)) return true;
+  return false;
 }
 
 // MPE entity table for the device env (multiagent/core.py Entity/Agent fields)

@@ -62,7 +62,7 @@ class Engine:
                  gamma=0.95, tau=1e-2, grad_clip=0.5, actor_reg=1e-3, adam_b1=0.9, adam_b2=0.999,
                  adam_eps=1e-8, seed=0, world_size=1, rank=0, device=None, episode_log_rows=0,
                  prioritized=False, per_alpha=0.6, per_beta0=0.4, per_beta_inc=0.001, per_eps=0.01,
-                 per_abs_err_upper=1.0, act_dims=None, td3=False, policy_delay=2, minimax=False, adv_eps=1e-3,
+                 per_abs_err_upper=1.0, act_dims=None, act_kinds=None, td3=False, policy_delay=2, minimax=False, adv_eps=1e-3,
                  adv_eps_s=1e-5, minimax_eps=None, approx=False, approx_lambda=1e-3):
         """approx: MADDPG with inferred policies (mdp_approx_enable; Lowe et al. 2017,
         section 4.2) -- every agent i with a MADDPG critic learns an approximator of
@@ -80,7 +80,13 @@ class Engine:
         critic step (1..8); strict mode, one GPU, no prioritized replay.
         act_dims: per-agent action widths A_i in 1..5 (Discrete(A_i)); None: 5 for
         every agent, or the scenario's own.  The device keeps every action slot 5
-        wide with zero pad entries; this class pads and slices at its boundary."""
+        wide with zero pad entries; this class pads and slices at its boundary.
+        act_kinds: per-agent "discrete" / "box" (or MDP_ACT_DISCRETE 0 / MDP_ACT_BOX 1)
+        beside act_dims (mdp_set_act_spaces): a "box" agent has a Box(act_dims[i])
+        space, act_dims[i] in {1, 2}, and a diagonal-Gaussian policy whose head
+        (actor_logits) is [mean | logstd], 2 act_dims[i] wide.  With a scenario,
+        act_dims may be None: a box agent is Box(2), the others keep their own
+        space.  Strict mode, one GPU, none of prioritized / td3 / minimax / approx."""
         self.lib = _lib.load()
         if not torch.cuda.is_available():
             raise RuntimeError("maddpg_amd runs on a ROCm GPU only (no CPU fallback)")
@@ -146,7 +152,19 @@ class Engine:
             self.h = None
             raise ValueError(f"mdp_create failed: {msg}")
         dims = (ctypes.c_int32 * _lib.MAX_AGENTS)()
-        if act_dims is not None:
+        if act_kinds is not None:
+            try:
+                if len(act_kinds) != n or (act_dims is not None and len(act_dims) != n):
+                    raise ValueError(f"act_kinds / act_dims need one entry for each of the {n} agents")
+                kinds = [self._act_kind(k) for k in act_kinds]
+                if act_dims is None:
+                    self._c("mdp_get_act_dims", dims)
+                    act_dims = [2 if kinds[i] == _lib.ACT_BOX else int(dims[i]) for i in range(n)]
+                self.set_act_spaces(kinds, act_dims)
+            except (ValueError, _lib.MdpError) as e:
+                self.close()
+                raise ValueError(str(e)) from None
+        elif act_dims is not None:
             if len(act_dims) != n:
                 self.close()
                 raise ValueError(f"act_dims has {len(act_dims)} entries for {n} agents")
@@ -162,6 +180,11 @@ class Engine:
             self.act_dims = [int(dims[i]) for i in range(n)]
         else:   # an older build chosen with MDP_LIB (A/B): every width is 5 there
             self.act_dims = [_lib.ACT_DIM] * n
+        self.act_kinds = ["discrete"] * n
+        if hasattr(self.lib, "mdp_get_act_spaces"):
+            kk = (ctypes.c_int32 * _lib.MAX_AGENTS)()
+            self._c("mdp_get_act_spaces", kk, None)
+            self.act_kinds = ["box" if kk[i] == _lib.ACT_BOX else "discrete" for i in range(n)]
         lay = (ctypes.c_int32 * 6)()
         self.row_layout = []
         for i in range(n):
@@ -269,6 +292,41 @@ class Engine:
         dims = (ctypes.c_int32 * _lib.MAX_AGENTS)(*[int(a) for a in act_dims])
         self._c("mdp_set_act_dims", dims)
 
+    @staticmethod
+    def _act_kind(k):
+        if k in ("discrete", _lib.ACT_DISCRETE):
+            return _lib.ACT_DISCRETE
+        if k in ("box", _lib.ACT_BOX):
+            return _lib.ACT_BOX
+        raise ValueError(f"unknown action kind {k!r} (discrete, box)")
+
+    def set_act_spaces(self, act_kinds, act_dims):
+        """mdp_set_act_spaces on this handle (refused once it has been used)"""
+        kinds = (ctypes.c_int32 * _lib.MAX_AGENTS)(*[self._act_kind(k) for k in act_kinds])
+        dims = (ctypes.c_int32 * _lib.MAX_AGENTS)(*[int(a) for a in act_dims])
+        self._c("mdp_set_act_spaces", kinds, dims)
+
+    def is_box(self, agent):
+        return self.act_kinds[agent] == "box"
+
+    def head_dim(self, agent):
+        """width of agent's actor head: A_i logits, or mean | logstd of a Box(d_i)"""
+        return self.act_dims[agent] * (2 if self.is_box(agent) else 1)
+
+    def pad_noise(self, agent, u):
+        """uniforms [..., k] -> the device's [..., 5] slot.  A Discrete(A_i) agent reads
+        the first A_i, a Box agent the first two (Box-Muller) whatever its width;
+        entries that are not given are never read and are set to 0.5"""
+        A = _lib.ACT_DIM
+        if u.shape[-1] == A:
+            return u
+        w = 2 if self.is_box(agent) else self.act_dims[agent]
+        if u.shape[-1] != w:
+            raise ValueError(f"agent {agent}: noise of width {u.shape[-1]}, it reads {w} uniforms")
+        out = u.new_full(u.shape[:-1] + (A,), 0.5)
+        out[..., :w] = u
+        return out
+
     def pad_act(self, agent, a):
         """[..., A_i] -> the device's [..., 5] slot with zero pad entries; an array
         that is already 5 wide passes as it is"""
@@ -312,6 +370,11 @@ class Engine:
         the six tensors (reshaped to their logical shapes) or a flat array"""
         shapes = self._flat_shapes(agent, which)
         if isinstance(params, dict):
+            for k, s in zip(TENSOR_NAMES, shapes):
+                if np.size(params[k]) != s[0] * s[1]:
+                    raise ValueError(f"agent {agent} {which}/{k}: shape {np.shape(params[k])} does not match the "
+                                     f"handle's {s} (its action space: {self.act_kinds[agent]} "
+                                     f"{self.act_dims[agent]})")
             parts = [np.asarray(params[k], np.float32).reshape(s) for k, s in zip(TENSOR_NAMES, shapes)]
             flat = np.concatenate([p.ravel() for p in parts])
         else:
@@ -810,11 +873,13 @@ class Engine:
 
     # ------------------------------------------------------------ policies
     def act(self, agent, obs, target=False, u=None):
-        """[rows, A_i] Gumbel-softmax samples; u: injected uniforms [rows, A_i] (or [rows, 5])"""
+        """[rows, A_i] Gumbel-softmax samples (a Box(d_i) agent: [rows, d_i] Gaussian
+        samples); u: injected uniforms [rows, A_i] (Box: [rows, 2]) or [rows, 5]"""
         obs = obs.to(self.device, torch.float32).contiguous()
         out = torch.empty((obs.shape[0], _lib.ACT_DIM), dtype=torch.float32, device=self.device)
         if u is not None:
-            u = self.pad_act(agent, u.to(self.device, torch.float32)).contiguous()
+            u = u.to(self.device, torch.float32)
+            u = (self.pad_noise(agent, u) if self.is_box(agent) else self.pad_act(agent, u)).contiguous()
             self._sized("u", u, obs.shape[0] * _lib.ACT_DIM)
         self.sync_in()
         self._c("mdp_act", agent, 1 if target else 0, self._ptr(obs), self._ptr(out), obs.shape[0], self._ptr(u))
@@ -831,7 +896,8 @@ class Engine:
         self.sync_in()
         self._c("mdp_actor_logits", agent, 1 if target else 0, self._ptr(obs), self._ptr(out), obs.shape[0])
         self.sync_out()
-        return self._narrow(agent, out)
+        w = self.head_dim(agent)    # a Box agent: flat = [mean | logstd]
+        return out if w == _lib.ACT_DIM else out[:, :w].contiguous()
 
     def q_values(self, agent, x, target=False):
         """x: the critic input in its logical width (A_j columns per action), or in

@@ -24,6 +24,17 @@ class Discrete:
         return f"Discrete({self.n})"
 
 
+class Box:
+    """Minimal stand-in for ``gym.spaces.Box`` with a 1-D shape (unbounded floats):
+    recognised by having a ``shape`` and no ``n``"""
+
+    def __init__(self, d):
+        self.shape = (int(d),)
+
+    def __repr__(self):
+        return f"Box({self.shape[0]},)"
+
+
 @dataclass
 class ScenarioSpec:
     name: str
@@ -31,22 +42,41 @@ class ScenarioSpec:
     num_adversaries: int
     obs_dims: List[int] = field(default_factory=list)
     act_dims: List[int] = field(default_factory=list)   # Discrete(A_i) per agent; empty: Discrete(5) each
+    act_kinds: List[str] = field(default_factory=list)  # "discrete" / "box" per agent; empty: discrete each
 
     def __post_init__(self):
         if not self.act_dims:
             self.act_dims = [ACT_DIM] * self.n_agents
+        if not self.act_kinds:
+            self.act_kinds = ["discrete"] * self.n_agents
 
     @property
     def action_space(self):
-        return [Discrete(a) for a in self.act_dims]
+        return [Box(a) if k == "box" else Discrete(a) for k, a in zip(self.act_kinds, self.act_dims)]
+
+    def continuous(self):
+        """the same scenario with continuous actions (environment.py's
+        discrete_action_space = False): every agent that moves and does not
+        speak gets a Box(2) space, its action the force itself; the speaker of
+        simple_speaker_listener keeps its Discrete(3) words.  (This mirrors what
+        the library decides from its own scenario table -- EnvDesc::movable and
+        env_silent in csrc/mdp_topo.h -- and mdp_set_act_spaces is the judge: a
+        scenario added there with a fixed or speaking agent needs its line here.)"""
+        kinds = ["discrete" if (self.name == "simple_speaker_listener" and i == 0) else "box"
+                 for i in range(self.n_agents)]
+        dims = [2 if k == "box" else a for k, a in zip(kinds, self.act_dims)]
+        return ScenarioSpec(self.name, self.n_agents, self.num_adversaries, list(self.obs_dims), dims, kinds)
 
     @property
     def observation_shapes(self):
         return [(o,) for o in self.obs_dims]
 
 
-def spec(name, n_agents=None, num_adversaries=None):
-    """Scenario table (upstream make_world defaults unless overridden)."""
+def spec(name, n_agents=None, num_adversaries=None, continuous=False):
+    """Scenario table (upstream make_world defaults unless overridden);
+    continuous: Box spaces where the scenario allows them (ScenarioSpec.continuous)."""
+    if continuous:
+        return spec(name, n_agents, num_adversaries).continuous()
     if name == "simple":
         return ScenarioSpec(name, 1, 0, [4])
     if name == "simple_spread":

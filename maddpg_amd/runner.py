@@ -47,14 +47,17 @@ class VecRunner:
                  train_every=100, world_size=1, rank=0, device=None, episode_log_rows=0, tau=1e-2,
                  grad_clip=0.5, actor_reg=1e-3, prioritized=False, per_alpha=0.6, per_beta0=0.4,
                  per_beta_inc=0.001, per_eps=0.01, per_abs_err_upper=1.0, td3=False, policy_delay=2,
-                 minimax=False, adv_eps=1e-3, adv_eps_s=1e-5, approx=False, approx_lambda=1e-3):
+                 minimax=False, adv_eps=1e-3, adv_eps_s=1e-5, approx=False, approx_lambda=1e-3,
+                 continuous=False):
+        if continuous and world_size > 1:
+            raise ValueError("--continuous-actions runs on one GPU (Box action spaces have no data-parallel variant)")
         if td3 and world_size > 1:
             raise ValueError("--td3 runs on one GPU (MATD3 has no data-parallel variant)")
         if minimax and world_size > 1:
             raise ValueError("--minimax runs on one GPU (M3DDPG has no data-parallel variant)")
         if approx and world_size > 1:
             raise ValueError("--approx-policies runs on one GPU (inferred policies have no data-parallel variant)")
-        sp = envs.spec(scenario, n_agents, scenario_adversaries)
+        sp = envs.spec(scenario, n_agents, scenario_adversaries, continuous=continuous)
         self.spec = sp
         n = sp.n_agents
         n_adv_pol = min(n, num_adversaries)                  # train.py:84
@@ -68,7 +71,8 @@ class VecRunner:
                           per_beta0=per_beta0, per_beta_inc=per_beta_inc, per_eps=per_eps,
                           per_abs_err_upper=per_abs_err_upper, td3=td3, policy_delay=policy_delay,
                           minimax=minimax, adv_eps=adv_eps, adv_eps_s=adv_eps_s, approx=approx,
-                          approx_lambda=approx_lambda)
+                          approx_lambda=approx_lambda,
+                          **({"act_kinds": sp.act_kinds, "act_dims": sp.act_dims} if continuous else {}))
         self.eng.init_params(seed)                           # identical replicas on every rank
         self.eng.seed_py_random(seed + rank)                 # per-rank index stream
         self.eng.env_reset()

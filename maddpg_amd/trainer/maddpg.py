@@ -76,14 +76,25 @@ class MADDPGAgentTrainer(AgentTrainer):
         self.act_space_n = act_space_n
         self.local_q_func = local_q_func
         check_model(model, args.num_units)
-        # one Discrete(k) space per agent, k in 1..5 (make_pdtype, distributions.py:413-415;
-        # the reference raises on anything else: its MultiDiscrete branch is commented out)
-        self.act_dims = []
+        # one space per agent (make_pdtype, distributions.py:408-422): Discrete(k), k in
+        # 1..5, or Box(d), d in {1, 2} -- an entry with a 1-D shape and no n (the reference
+        # raises on anything else: its MultiDiscrete branch is commented out)
+        self.act_dims, self.act_kinds = [], []
         for sp in act_space_n:
+            shape = getattr(sp, "shape", None)
+            if not hasattr(sp, "n") and shape is not None and len(tuple(shape)) == 1:
+                d = int(tuple(shape)[0])
+                if d not in (1, 2):
+                    raise NotImplementedError(f"action space {sp!r}: Box(d) is supported for d in (1, 2)")
+                self.act_dims.append(d)
+                self.act_kinds.append("box")
+                continue
             k = getattr(sp, "n", 5)
             if not isinstance(k, (int, np.integer)) or not 1 <= int(k) <= 5:
-                raise NotImplementedError(f"action space {sp!r}: only Discrete(k), 1 <= k <= 5, is supported")
+                raise NotImplementedError(f"action space {sp!r}: only Discrete(k), 1 <= k <= 5, and Box(d), "
+                                          "d in (1, 2), are supported")
             self.act_dims.append(int(k))
+            self.act_kinds.append("discrete")
         self.session = U.get_session()
         self.session.register(self)
         self.replay_buffer = ReplayBuffer(1e6, _session=self.session, _agent=agent_index)

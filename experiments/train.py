@@ -417,78 +417,48 @@ def train(arglist):
     return _train(arglist, runner, exp_name, world, rank)
 
 
+def _combination(flag, arglist, world):
+    """each variant flag (maddpg_amd/variants.py) runs alone, in strict mode, on one
+    GPU: refuse the combinations the library has no variant for before anything is built"""
+    from maddpg_amd.variants import flag_refusal
+    why = flag_refusal(flag, arglist, world)
+    if why:
+        raise SystemExit(why)
+
+
 def td3_flags(arglist, world=1):
-    """--td3 is MATD3 on one GPU in strict mode with npz checkpoints: refuse the
-    combinations the library has no variant for before anything is built"""
+    """--td3 is MATD3, with npz checkpoints"""
     if not getattr(arglist, "td3", False):
         return
     if not 1 <= arglist.policy_delay <= 8:
         raise SystemExit("--policy-delay must be in 1..8")
-    if arglist.prioritized_replay:
-        raise SystemExit("--td3 does not combine with --prioritized-replay")
-    if arglist.update_mode != "strict":
-        raise SystemExit("--td3 needs --update-mode strict")
-    if (arglist.num_gpus or 1) > 1 or world > 1:
-        raise SystemExit("--td3 runs on one GPU (--num-gpus 1)")
-    if arglist.save_format == "tf1":
-        raise SystemExit("--td3 saves npz checkpoints only (the second critic has no reference variable names)")
+    _combination("--td3", arglist, world)
 
 
 def continuous_flags(arglist, world=1):
-    """--continuous-actions is Box spaces on one GPU in strict mode: refuse the
-    combinations the library has no variant for before anything is built"""
-    if not getattr(arglist, "continuous_actions", False):
-        return
-    for flag, on in (("--prioritized-replay", arglist.prioritized_replay), ("--td3", arglist.td3),
-                     ("--minimax", arglist.minimax), ("--approx-policies", arglist.approx_policies)):
-        if on:
-            raise SystemExit(f"--continuous-actions does not combine with {flag}")
-    if arglist.update_mode != "strict":
-        raise SystemExit("--continuous-actions needs --update-mode strict")
-    if (arglist.num_gpus or 1) > 1 or world > 1:
-        raise SystemExit("--continuous-actions runs on one GPU (--num-gpus 1)")
+    """--continuous-actions is Box spaces"""
+    _combination("--continuous-actions", arglist, world)
 
 
 def minimax_flags(arglist, world=1):
-    """--minimax is M3DDPG on one GPU in strict mode: refuse the combinations the
-    library has no variant for before anything is built"""
+    """--minimax is M3DDPG"""
     if not getattr(arglist, "minimax", False):
         return
     for name in ("adv_eps", "adv_eps_s"):
         v = getattr(arglist, name)
         if not (v >= 0 and v != float("inf")):
             raise SystemExit(f"--{name.replace('_', '-')} must be finite and >= 0")
-    if arglist.td3:
-        raise SystemExit("--minimax does not combine with --td3")
-    if arglist.prioritized_replay:
-        raise SystemExit("--minimax does not combine with --prioritized-replay")
-    if arglist.update_mode != "strict":
-        raise SystemExit("--minimax needs --update-mode strict")
-    if (arglist.num_gpus or 1) > 1 or world > 1:
-        raise SystemExit("--minimax runs on one GPU (--num-gpus 1)")
+    _combination("--minimax", arglist, world)
 
 
 def approx_flags(arglist, world=1):
-    """--approx-policies is MADDPG with inferred policies on one GPU in strict mode:
-    refuse the combinations the library has no variant for before anything is built"""
+    """--approx-policies is MADDPG with inferred policies, with npz checkpoints"""
     if not getattr(arglist, "approx_policies", False):
         return
     lam = arglist.approx_lambda
     if not (lam >= 0 and lam != float("inf")):
         raise SystemExit("--approx-lambda must be finite and >= 0")
-    if arglist.prioritized_replay:
-        raise SystemExit("--approx-policies does not combine with --prioritized-replay")
-    if arglist.td3:
-        raise SystemExit("--approx-policies does not combine with --td3")
-    if arglist.minimax:
-        raise SystemExit("--approx-policies does not combine with --minimax")
-    if arglist.update_mode != "strict":
-        raise SystemExit("--approx-policies needs --update-mode strict")
-    if (arglist.num_gpus or 1) > 1 or world > 1:
-        raise SystemExit("--approx-policies runs on one GPU (--num-gpus 1)")
-    if getattr(arglist, "save_format", "npz") == "tf1":
-        raise SystemExit("--approx-policies saves npz checkpoints only (the approximators have no reference "
-                         "variable names)")
+    _combination("--approx-policies", arglist, world)
 
 
 def _make_runner(arglist, VecRunner, world, rank, per):

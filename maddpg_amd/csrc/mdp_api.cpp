@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "mdp_kernels.h"
+#include "mdp_variants.h"
 
 namespace {
 
@@ -398,11 +399,12 @@ struct mdp_handle {
   uint32_t x_probe_ep = 0;
   bool p2p = false;
   bool xw_stats = false;              // stamp the exchange waits (mdp_dp_exchange_stats_enable)
+  // the one training variant of this handle (mdp_variants.h; its own state follows)
+  Variant variant = Variant::None;
   // prioritized replay (mdp_per_enable): the caller's second device buffer --
   // cursor, per-agent beta / sample counter, per-agent index / weight / |TD
   // error| slots [n][B], one sum tree per agent
-  bool per = false;
-  bool trained = false;               // an update / train call was made (mdp_per_enable must precede it)
+  bool trained = false;               // an update / train call was made (a variant's enable must precede it)
   bool started = false;               // a parameter write, act, update or env call was made (mdp_set_act_dims must precede it)
   PerHdr* per_hdr = nullptr;
   PerState* per_st = nullptr;
@@ -415,14 +417,17 @@ struct mdp_handle {
   // MATD3 (mdp_td3_enable): the caller's TD3 buffer -- the second critic's five
   // param-space regions (the arena's offsets; actor spans unused), its partials
   // and records, beta powers, stats and its optimizer's own sync area
-  bool td3 = false;
   int td3_delay = 2;
+  // an optimizer's own sync area in a side buffer (sync_take, sync_bind)
+  struct SyncArea {
+    uint32_t *ticket = nullptr, *ctr = nullptr;
+    uint64_t* part = nullptr;
+  };
   struct Critic2 {
     float *theta = nullptr, *target = nullptr, *m = nullptr, *v = nullptr, *grad = nullptr;
     float *slab = nullptr, *beta = nullptr;
     double *stat = nullptr, *stats = nullptr;
-    uint32_t *ticket = nullptr, *ctr = nullptr;
-    uint64_t* part = nullptr;
+    SyncArea sync;
   } c2;
   // updates of agent i since enable: committed once the launch or replay was
   // issued (td3_count), and as the launches being issued or captured see it (td3_work)
@@ -430,22 +435,19 @@ struct mdp_handle {
   int64_t td3_work[MDP_MAX_AGENTS] = {};
   // M3DDPG (mdp_minimax_enable): eps[i][j], and the debug buffers that receive
   // the moved actions of the critic / actor step (mdp_minimax_debug_adv)
-  bool minimax = false;
   float mm_eps[MDP_MAX_AGENTS][MDP_MAX_AGENTS] = {};
   float *mm_adv_c = nullptr, *mm_adv_a = nullptr;
   // inferred policies (mdp_approx_enable): the caller's buffer -- per observing
   // agent five param-space regions (net, target, m, v, grad), then the shared
   // partials, the records [n][n][nwg][8], beta powers [n][n][4] and the
   // optimizer launches' own sync area (one slot per approximated agent)
-  bool approx = false;
   float apx_lambda = 1e-3f;
   struct Approx {
     char* buf = nullptr;
     int64_t region = 0, obs_stride = 0;  // bytes
     float *slab = nullptr, *beta = nullptr;
     double* stat = nullptr;
-    uint32_t *ticket = nullptr, *ctr = nullptr;
-    uint64_t* part = nullptr;
+    SyncArea sync;
   } apx;
   int64_t apx_count[MDP_MAX_AGENTS] = {};  // approximator steps of observer i so far
   int apx_pending = -1;  // observer whose gradient-only launch (mdp_approx_grad) the partials hold, or -1
@@ -462,6 +464,22 @@ int fail(mdp_handle* h, const char* what, hipError_t e = hipSuccess) {
     }
   }
   return -1;
+}
+
+const VariantInfo& info(const mdp_handle* h) { return variant_info(h->variant); }
+
+// the one place a handle's variant, Box space, update mode or data parallelism
+// refuses a call: what mdp_variants.h's refusal() says of this handle at `at`
+int gate(mdp_handle* h, Seam at, Variant enabling = Variant::None) {
+  GateState s;
+  s.variant = h->variant;
+  s.box = h->box;
+  s.trained = h->trained;
+  s.update_mode = h->update_mode;
+  s.dp_joined = h->comm || h->p2p || h->xbuf;
+  s.dp_world = h->cfg.world_size > 1;
+  const std::string why = refusal(s, at, enabling);
+  return why.empty() ? 0 : fail(h, why.c_str());
 }
 
 #define HIPCHK(h, call)                        \
@@ -622,7 +640,7 @@ int region_for(int which, int* region, int* net) {
 // null with the reason in the handle's error
 float* which_base(mdp_handle* h, int which, int* net) {
   if (which >= MDP_CRITIC2 && which <= MDP_G_CRITIC2) {
-    if (!h->td3) {
+    if (h->variant != Variant::Td3) {
       fail(h, "which: the second critic's sets (10..14) need MATD3 (mdp_td3_enable)");
       return nullptr;
     }
@@ -824,12 +842,12 @@ CriticArgsPer per_critic_args(mdp_handle* h, const CriticArgs& a) {
 // M3DDPG: agent's steps run the minimax instantiations -- a MADDPG critic that
 // sees another agent's action (a DDPG critic sees none: today's kernels, bit for bit)
 bool mm_agent(const mdp_handle* h, int agent) {
-  return h->minimax && !h->L.topo.ag[agent].local_q && h->cfg.n_agents > 1;
+  return h->variant == Variant::Minimax && !h->L.topo.ag[agent].local_q && h->cfg.n_agents > 1;
 }
 
 // inferred policies: agent has approximators -- a MADDPG critic and someone to approximate
 bool apx_agent(const mdp_handle* h, int agent) {
-  return h->approx && !h->L.topo.ag[agent].local_q && h->cfg.n_agents > 1;
+  return h->variant == Variant::Approx && !h->L.topo.ag[agent].local_q && h->cfg.n_agents > 1;
 }
 // param-space base of set k (mdp_approx_set) of observer's approximators
 float* apx_base(const mdp_handle* h, int observer, int k) {
@@ -849,7 +867,7 @@ int do_critic_grad(mdp_handle* h, int agent, const int32_t* idx, const float* u_
     if (apre) a.apre = h->apre;
     if (post_prev >= 0) a.cpre = h->cpre;
     if (h->grad_twin) a.twin = 2;
-    if (h->per)
+    if (h->variant == Variant::Per)
       HIPCHK(h, mdp_launch_critic_grad_r_per(per_critic_args(h, a), lds_critic_r_bytes(h->L.topo, agent), h->stream));
     else
       HIPCHK(h, mdp_launch_critic_grad_r(a, lds_critic_r_bytes(h->L.topo, agent), h->stream));
@@ -874,7 +892,7 @@ int do_critic_grad(mdp_handle* h, int agent, const int32_t* idx, const float* u_
     HIPCHK(h, mdp_launch_critic_grad_apx(x, h->L.topo.H, lds_critic_bytes(h->L.topo, a.group), h->stream));
     return 0;
   }
-  if (h->per && !tp)
+  if (h->variant == Variant::Per && !tp)
     HIPCHK(h, mdp_launch_critic_grad_per(per_critic_args(h, a), h->L.topo.H, lds_critic_bytes(h->L.topo, a.group),
                                          h->stream));
   else
@@ -1015,9 +1033,9 @@ OptNet opt_critic2(mdp_handle* h, int agent, int bump) {
   o.slab_stat = c.stat;
   o.y = h->y;
   o.stats_out = c.stats + agent * 8;
-  o.ticket = c.ticket;
-  o.ctr = c.ctr;
-  o.part = c.part;
+  o.ticket = c.sync.ticket;
+  o.ctr = c.sync.ctr;
+  o.part = c.sync.part;
   o.slot = agent;
   o.polyak = 0;
   o.stats_mode = 1;
@@ -1040,9 +1058,9 @@ OptNet opt_approx(mdp_handle* h, int observer, int j, int p) {
   o.grad = apx_base(h, observer, MDP_APX_GRAD);
   o.slab = x.slab + (int64_t)p * h->L.nwg * h->L.slab_a;
   o.beta = x.beta + ((int64_t)observer * h->cfg.n_agents + j) * 4;
-  o.ticket = x.ticket;
-  o.ctr = x.ctr;
-  o.part = x.part;
+  o.ticket = x.sync.ticket;
+  o.ctr = x.sync.ctr;
+  o.part = x.sync.part;
   o.slot = j;
   o.polyak = 0;
   o.stats_mode = 0;
@@ -1421,7 +1439,7 @@ int do_update(mdp_handle* h, int agent, const int32_t* idx, const float* u_tgt, 
   // data parallel: the exchange runs whatever the noise source (injected
   // uniforms included -- an update that skipped it would split the replicas)
   if (h->comm || h->p2p) return do_update_dp(h, agent, idx, u_tgt, u_act, pf_out, post_prev, pre_next, pre_idx, dp);
-  if (h->td3) return do_update_td3(h, agent, idx, u_tgt, u_act);
+  if (h->variant == Variant::Td3) return do_update_td3(h, agent, idx, u_tgt, u_act);
   int rc;
   const bool fused = h->fused_apply && reduce_apply_ok(h, agent, 0) && reduce_apply_ok(h, agent, 1);
   const bool pre = actor_pre_ok(h, agent);
@@ -1842,21 +1860,30 @@ int per_update(mdp_handle* h, int agent0, int agents, int count, const int32_t* 
   return 0;
 }
 
-const char* kPerNoDp = "prioritized replay runs on one GPU in strict mode: no data-parallel exchange";
-const char* kBoxOnly =
-    "a handle with a Box action space (mdp_set_act_spaces) trains in strict mode on one GPU: no prioritized replay, "
-    "MATD3, M3DDPG, inferred policies, throughput mode or data parallelism";
-const char* kTd3NoDp = "MATD3 (mdp_td3_enable) runs on one GPU in strict mode: no data-parallel exchange";
-const char* kMmNoDp = "M3DDPG (mdp_minimax_enable) runs on one GPU in strict mode: no data-parallel exchange";
-
 // an optimizer's own sync area for one net per agent (mdp_ra_sync_bytes holds the
 // arena's two): per slot 8 counters x 128 B, then per slot [6][MDP_RA_MAXCH][2] tagged words
 const int64_t kSyncCtrBytes = (int64_t)MDP_MAX_AGENTS * 8 * 128;
 const int64_t kSyncPartBytes = (int64_t)MDP_MAX_AGENTS * 6 * MDP_RA_MAXCH * 16;
+struct SyncLayout {
+  int64_t ticket, ctr, part;
+};
+// the area's three parts, taken in this order from a side buffer's layout
+template <class Take>
+SyncLayout sync_take(Take& take) {
+  SyncLayout s;
+  s.ticket = take(256);
+  s.ctr = take(kSyncCtrBytes);
+  s.part = take(kSyncPartBytes);
+  return s;
+}
+mdp_handle::SyncArea sync_bind(char* b, const SyncLayout& s) {
+  return {(uint32_t*)(b + s.ticket), (uint32_t*)(b + s.ctr), (uint64_t*)(b + s.part)};
+}
 
 // byte offsets inside the caller's TD3 buffer
 struct Td3Layout {
-  int64_t theta, target, m, v, grad, slab, stat, beta, stats, ticket, ctr, part, total;
+  int64_t theta, target, m, v, grad, slab, stat, beta, stats, total;
+  SyncLayout sync;  // one slot per agent
 };
 Td3Layout td3_layout(const mdp_config& c, const Layout& L) {
   Td3Layout t;
@@ -1875,18 +1902,15 @@ Td3Layout td3_layout(const mdp_config& c, const Layout& L) {
   t.stat = take(8 * 8 * (int64_t)L.nwg);
   t.beta = take(4 * 4 * (int64_t)c.n_agents);
   t.stats = take(8 * 8 * (int64_t)c.n_agents);
-  t.ticket = take(256);
-  t.ctr = take(kSyncCtrBytes);  // one slot per agent
-  t.part = take(kSyncPartBytes);
+  t.sync = sync_take(take);
   t.total = o;
   return t;
 }
 
-const char* kApxNoDp = "inferred policies (mdp_approx_enable) run on one GPU in strict mode: no data-parallel exchange";
-
 // byte offsets inside the caller's approximator buffer
 struct ApxLayout {
-  int64_t region, obs_stride, slab, stat, beta, ticket, ctr, part, total;
+  int64_t region, obs_stride, slab, stat, beta, total;
+  SyncLayout sync;  // one slot per approximated agent
 };
 ApxLayout apx_layout(const mdp_config& c, const Layout& L) {
   ApxLayout t;
@@ -1902,11 +1926,48 @@ ApxLayout apx_layout(const mdp_config& c, const Layout& L) {
   t.slab = take(4 * std::max<int64_t>(n - 1, 1) * L.nwg * L.slab_a);
   t.stat = take(8 * 8 * n * n * L.nwg);
   t.beta = take(4 * 4 * n * n);
-  t.ticket = take(256);
-  t.ctr = take(kSyncCtrBytes);  // one slot per approximated agent
-  t.part = take(kSyncPartBytes);
+  t.sync = sync_take(take);
   t.total = o;
   return t;
+}
+
+// an entry point `fn` that serves variant v only, on a handle without it
+int need_variant(mdp_handle* h, const char* fn, Variant v) {
+  if (h->variant == v) return 0;
+  const VariantInfo& vi = variant_info(v);
+  return fail(h, (std::string(fn) + ": " + vi.name + verb(v, " is", " are") + " not enabled (" + vi.enable + ")").c_str());
+}
+
+// v's enable went through: from here the handle is v's.  A variant of the
+// general kernels has no actor_pre / critic_pre and no index prefetch; every
+// graph captured before is another variant's
+void set_variant(mdp_handle* h, Variant v) {
+  h->variant = v;
+  if (variant_info(v).general_kernels) h->general_grads = true;
+  destroy_graphs(h, true);
+}
+
+// `count` optimizers' beta powers at dst: the next powers (TF1's variables) and
+// this step's, both starting at beta; the stream is idle when this returns
+int write_beta_powers(mdp_handle* h, float* dst, int count) {
+  std::vector<float> beta(4 * (size_t)count);
+  for (int i = 0; i < count; ++i) {
+    beta[4 * i] = beta[4 * i + 2] = h->cfg.adam_b1;
+    beta[4 * i + 1] = beta[4 * i + 3] = h->cfg.adam_b2;
+  }
+  HIPCHK(h, hipMemcpyAsync(dst, beta.data(), 4 * beta.size(), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  return 0;
+}
+
+// the caller's side buffer of enable `fn`: `total` bytes of the handle's device
+// (`sizer` reports them), all zeroed once the stream's earlier work is done
+int take_side_buffer(mdp_handle* h, const char* fn, const char* sizer, void* buf_dev, int64_t bytes, int64_t total) {
+  if (buf_dev && bytes < total) return fail(h, (std::string(fn) + ": bytes is smaller than " + sizer).c_str());
+  MDP_DEV(h, buf_dev, total, fn, false);
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  HIPCHK(h, hipMemsetAsync(buf_dev, 0, total, h->stream));
+  return 0;
 }
 
 // ---- host counters and the graph cache of the training entry points
@@ -1918,19 +1979,19 @@ void td3_begin(mdp_handle* h) {
 // the host-side counts of `rounds` whole rounds that went out: the approximators'
 // step counts (inferred policies) and MATD3's update counts; a plain handle has neither
 void commit_rounds(mdp_handle* h, int rounds) {
-  if (h->approx && rounds > 0) {  // inferred policies: every observer's pairs stepped once per round
+  if (h->variant == Variant::Approx && rounds > 0) {  // inferred policies: every observer's pairs stepped once per round
     for (int i = 0; i < h->cfg.n_agents; ++i)
       if (apx_agent(h, i)) h->apx_count[i] += rounds;
     h->apx_pending = -1;
   }
-  if (!h->td3) return;
+  if (h->variant != Variant::Td3) return;
   for (int i = 0; i < h->cfg.n_agents; ++i) h->td3_count[i] += rounds;
 }
 // key of a captured graph.  With MATD3 what is captured depends on which agents
 // are due for an actor step: every agent's committed count mod the delay
 std::vector<int> graph_key(const mdp_handle* h, int kind, const std::vector<int>& ks) {
   std::vector<int> key{kind};
-  if (h->td3)
+  if (h->variant == Variant::Td3)
     for (int i = 0; i < h->cfg.n_agents; ++i) key.push_back((int)(h->td3_count[i] % h->td3_delay));
   key.insert(key.end(), ks.begin(), ks.end());
   return key;
@@ -2109,12 +2170,7 @@ int mdp_create(const mdp_config* cfg, void* arena_dev, int64_t arena_bytes, void
     h->cpre_rows = h->apre_rows + (int64_t)nwg * 16 * h->L.topo.row_stride;
   }
   HIPCHK(h, hipMemsetAsync(h->arena, 0, h->L.total, h->stream));
-  std::vector<float> beta(8 * cfg->n_agents);
-  for (int i = 0; i < cfg->n_agents * 2; ++i) {  // TF1: beta powers start at beta
-    beta[4 * i] = beta[4 * i + 2] = cfg->adam_b1;
-    beta[4 * i + 1] = beta[4 * i + 3] = cfg->adam_b2;
-  }
-  HIPCHK(h, hipMemcpyAsync(h->beta, beta.data(), 4 * beta.size(), hipMemcpyHostToDevice, h->stream));
+  if (write_beta_powers(h, h->beta, 2 * cfg->n_agents)) return -1;  // TF1: beta powers start at beta
   Ctl c;
   std::memset(&c, 0, sizeof(c));
   py_seed_state(0, c.mt, &c.mt_pos);
@@ -2231,12 +2287,7 @@ int mdp_set_act_spaces(mdp_handle* h, const int32_t kinds[MDP_MAX_AGENTS], const
       }
     }
   }
-  if (box) {
-    if (h->per || h->td3 || h->minimax || h->approx)
-      return fail(h, (std::string("mdp_set_act_spaces: ") + kBoxOnly).c_str());
-    if (h->update_mode != 0 || h->comm || h->xbuf || h->p2p)
-      return fail(h, (std::string("mdp_set_act_spaces: ") + kBoxOnly).c_str());
-  }
+  if (box && gate(h, Seam::BoxSpace)) return -1;
   for (int i = 0; i < n; ++i) topo_set_act_space(h->L.topo, i, kinds[i] == MDP_ACT_BOX, dims[i]);
   h->box = box;
   return 0;
@@ -2291,13 +2342,13 @@ int mdp_get_params(mdp_handle* h, int32_t agent, int32_t which, float* dst, int6
 
 int mdp_get_beta_powers(mdp_handle* h, int32_t agent, int32_t net, float out2[2]) {
   if (bad_agent(h, agent)) return -1;
-  if (net == 2 && !h->td3) return fail(h, "mdp_get_beta_powers: net 2 (the second critic) needs MATD3 (mdp_td3_enable)");
+  if (net == 2 && h->variant != Variant::Td3) return fail(h, "mdp_get_beta_powers: net 2 (the second critic) needs MATD3 (mdp_td3_enable)");
   return read_beta_powers(h, net == 2 ? h->c2.beta + agent * 4 : h->beta + agent * 8 + (net ? 4 : 0), out2);
 }
 
 int mdp_set_beta_powers(mdp_handle* h, int32_t agent, int32_t net, const float in2[2]) {
   if (bad_agent(h, agent)) return -1;
-  if (net == 2 && !h->td3) return fail(h, "mdp_set_beta_powers: net 2 (the second critic) needs MATD3 (mdp_td3_enable)");
+  if (net == 2 && h->variant != Variant::Td3) return fail(h, "mdp_set_beta_powers: net 2 (the second critic) needs MATD3 (mdp_td3_enable)");
   return write_beta_powers(h, net == 2 ? h->c2.beta + agent * 4 : h->beta + agent * 8 + (net ? 4 : 0), in2);
 }
 
@@ -2317,7 +2368,7 @@ int mdp_buffer_add_rows(mdp_handle* h, const float* rows_dev, int64_t rows) {
   HIPCHK(h, mdp_launch_put_rows(h->replay, h->L.topo.row_stride, cap, start,
                                 rows_dev + skip * h->L.topo.row_stride, rows - skip, h->stream));
   const int rc = set_ring(h, std::min(cap, h->len + rows), (h->next + rows) % cap);
-  if (rc || !h->per) return rc;
+  if (rc || h->variant != Variant::Per) return rc;
   return per_sync(h, rows, false);  // the new rows' leaves
 }
 
@@ -2335,7 +2386,7 @@ int mdp_buffer_set_len(mdp_handle* h, int64_t len, int64_t next_idx) {
   MDP_NEED(h);
   if (len < 0 || len > h->cfg.capacity || next_idx < 0 || next_idx >= h->cfg.capacity)
     return fail(h, "ring state out of range");
-  if (!h->per) return set_ring(h, len, next_idx);
+  if (h->variant != Variant::Per) return set_ring(h, len, next_idx);
   // prioritized replay: a plain advance of the head makes those rows new; any
   // other change of the ring state rebuilds every leaf from the new length
   const int64_t cap = h->cfg.capacity, rows = (next_idx - h->next + cap) % cap;
@@ -2350,7 +2401,7 @@ int mdp_buffer_set_ring(mdp_handle* h, int64_t len, int64_t next_idx, int64_t ro
   MDP_NEED(h);
   if (len < 0 || len > h->cfg.capacity || next_idx < 0 || next_idx >= h->cfg.capacity || rows_total < 0)
     return fail(h, "ring state out of range");
-  if (!h->per) return set_ring(h, len, next_idx);
+  if (h->variant != Variant::Per) return set_ring(h, len, next_idx);
   // prioritized replay: exactly the rows added since the last call are new (a
   // count, not a difference of ring heads: it survives any number of wraps; at
   // least `capacity` of them reset every filled leaf).  A state that does not
@@ -2500,7 +2551,7 @@ int mdp_update(mdp_handle* h, int32_t agent, const int32_t* idx_dev, const float
   MDP_DEV(h, u_tgt_dev, 4 * n * B * MDP_ACT_DIM, "mdp_update", true);
   MDP_DEV(h, u_act_dev, 4 * B * MDP_ACT_DIM, "mdp_update", true);
   h->trained = true;
-  if (h->per) {
+  if (h->variant == Variant::Per) {
     // this agent's tree gives the rows (or, for given rows, their weights: beta
     // advances the same way); the critic step's |TD errors| go back as priorities
     if (h->len <= 0) return fail(h, "update on an empty replay buffer");
@@ -2520,7 +2571,7 @@ int mdp_update(mdp_handle* h, int32_t agent, const int32_t* idx_dev, const float
   }
   td3_begin(h);
   const int rc = do_update(h, agent, idx, u_tgt_dev, u_act_dev);
-  if (!rc && h->td3) h->td3_count[agent] += 1;
+  if (!rc && h->variant == Variant::Td3) h->td3_count[agent] += 1;
   if (!rc && apx_agent(h, agent)) {
     h->apx_count[agent] += 1;
     h->apx_pending = -1;
@@ -2645,7 +2696,7 @@ static int per_round_launches(mdp_handle* h, bool sync) {
 
 static int round_launches(mdp_handle* h) {
   const int n = h->cfg.n_agents, B = h->cfg.batch_size;
-  if (h->per) return per_round_launches(h, true);
+  if (h->variant == Variant::Per) return per_round_launches(h, true);
   int rc = launch_make_index(h, n * B, h->index);
   if (rc) return rc;
   return round_updates(h, h->index);
@@ -2700,12 +2751,7 @@ int mdp_dp_unique_id(uint8_t* out128) {
 
 int mdp_dp_init(mdp_handle* h, const uint8_t* id128, int32_t world, int32_t rank) {
   if (unusable(h) || !id128) return -1;
-  if (h->box) return fail(h, (std::string("mdp_dp_init: ") + kBoxOnly).c_str());
-  if (h->per) return fail(h, kPerNoDp);
-  if (h->td3) return fail(h, (std::string("mdp_dp_init: ") + kTd3NoDp).c_str());
-  if (h->minimax) return fail(h, (std::string("mdp_dp_init: ") + kMmNoDp).c_str());
-  if (h->approx) return fail(h, (std::string("mdp_dp_init: ") + kApxNoDp).c_str());
-  if (h->update_mode != 0) return fail(h, "join data parallelism before choosing the throughput mode");
+  if (gate(h, Seam::DpInit)) return -1;
   if (h->p2p || h->xbuf) return fail(h, "mdp_dp_init: the xGMI exchange is already set up");
   if (!rccl().ok) return fail(h, "librccl.so.1 could not be loaded");
   if (world < 1 || rank < 0 || rank >= world) return fail(h, "mdp_dp_init: bad world/rank");
@@ -2730,12 +2776,7 @@ int mdp_dp_init(mdp_handle* h, const uint8_t* id128, int32_t world, int32_t rank
 
 int mdp_dp_xgmi_open(mdp_handle* h, int32_t world, int32_t rank, uint8_t* handle_out) {
   if (unusable(h) || !handle_out) return -1;
-  if (h->box) return fail(h, (std::string("mdp_dp_xgmi_open: ") + kBoxOnly).c_str());
-  if (h->per) return fail(h, kPerNoDp);
-  if (h->td3) return fail(h, (std::string("mdp_dp_xgmi_open: ") + kTd3NoDp).c_str());
-  if (h->minimax) return fail(h, (std::string("mdp_dp_xgmi_open: ") + kMmNoDp).c_str());
-  if (h->approx) return fail(h, (std::string("mdp_dp_xgmi_open: ") + kApxNoDp).c_str());
-  if (h->update_mode != 0) return fail(h, "join data parallelism before choosing the throughput mode");
+  if (gate(h, Seam::XgmiOpen)) return -1;
   if (h->comm) return fail(h, "mdp_dp_xgmi_open: an RCCL communicator is already set up");
   if (h->xbuf) return fail(h, "mdp_dp_xgmi_open: already open");
   if (world < 2 || world > MDP_XCH_MAXW || rank < 0 || rank >= world)
@@ -2764,7 +2805,7 @@ int mdp_dp_xgmi_open(mdp_handle* h, int32_t world, int32_t rank, uint8_t* handle
 
 int mdp_dp_xgmi_connect(mdp_handle* h, const uint8_t* handles) {
   if (unusable(h) || !handles) return -1;
-  if (h->box) return fail(h, (std::string("mdp_dp_xgmi_connect: ") + kBoxOnly).c_str());
+  if (gate(h, Seam::XgmiConnect)) return -1;
   if (!h->xbuf) return fail(h, "mdp_dp_xgmi_connect: call mdp_dp_xgmi_open first");
   if (!h->x_opened.empty()) return fail(h, "mdp_dp_xgmi_connect: already connected");
   const int W = h->x_world, r = h->x_rank;
@@ -2792,7 +2833,7 @@ int mdp_dp_xgmi_connect(mdp_handle* h, const uint8_t* handles) {
 
 int mdp_dp_xgmi_probe(mdp_handle* h, int32_t* mismatches) {
   if (unusable(h)) return -1;
-  if (h->box) return fail(h, (std::string("mdp_dp_xgmi_probe: ") + kBoxOnly).c_str());
+  if (gate(h, Seam::XgmiProbe)) return -1;
   if (!h->xd_dev) return fail(h, "mdp_dp_xgmi_probe: not connected");
   const int nchunk = MDP_XCH_PROBE / 256;
   HIPCHK(h, hipMemsetAsync(h->x_probe, 0, 2 * sizeof(uint32_t), h->stream));
@@ -2809,14 +2850,9 @@ int mdp_dp_xgmi_probe(mdp_handle* h, int32_t* mismatches) {
 
 int mdp_dp_xgmi_enable(mdp_handle* h) {
   if (unusable(h)) return -1;
-  if (h->box) return fail(h, (std::string("mdp_dp_xgmi_enable: ") + kBoxOnly).c_str());
-  // (an approx handle never gets past mdp_dp_xgmi_open, so say why before "not connected")
-  if (h->approx) return fail(h, (std::string("mdp_dp_xgmi_enable: ") + kApxNoDp).c_str());
+  // (a variant's handle never gets past mdp_dp_xgmi_open, so say why before "not connected")
+  if (gate(h, Seam::XgmiEnable)) return -1;
   if (!h->xd_dev) return fail(h, "mdp_dp_xgmi_enable: not connected");
-  if (h->per) return fail(h, kPerNoDp);
-  if (h->td3) return fail(h, (std::string("mdp_dp_xgmi_enable: ") + kTd3NoDp).c_str());
-  if (h->minimax) return fail(h, (std::string("mdp_dp_xgmi_enable: ") + kMmNoDp).c_str());
-  if (h->update_mode != 0) return fail(h, "join data parallelism before choosing the throughput mode");
   HIPCHK(h, hipStreamSynchronize(h->stream));
   h->p2p = true;
   h->dp_world = h->x_world;
@@ -2886,14 +2922,7 @@ int mdp_set_update_mode(mdp_handle* h, int32_t mode) {
   if (unusable(h)) return -1;
   if (mode != 0 && mode != 1) return fail(h, "update mode must be 0 (strict) or 1 (throughput)");
   if (mode == 1) {
-    if (h->box) return fail(h, (std::string("mdp_set_update_mode: ") + kBoxOnly).c_str());
-    if (h->td3) return fail(h, "mdp_set_update_mode: mode 1 (throughput) is not supported with MATD3 (mdp_td3_enable)");
-    if (h->minimax)
-      return fail(h, "mdp_set_update_mode: mode 1 (throughput) is not supported with M3DDPG (mdp_minimax_enable)");
-    if (h->approx)
-      return fail(h, "mdp_set_update_mode: mode 1 (throughput) is not supported with inferred policies "
-                     "(mdp_approx_enable)");
-    if (h->per) return fail(h, "prioritized replay needs the strict update mode (throughput mode is not supported)");
+    if (gate(h, Seam::SetThroughput)) return -1;
     if (!tp_ok(h)) return fail(h, "throughput mode needs the fused optimizer step for every net and <= 8 agents");
     HIPCHK(h, hipStreamSynchronize(h->stream));
     if (tp_setup(h)) return -1;
@@ -2908,11 +2937,7 @@ int mdp_set_update_mode(mdp_handle* h, int32_t mode) {
 
 int mdp_update_all(mdp_handle* h, const int32_t* idx_dev, const float* u_tgt_dev, const float* u_act_dev) {
   if (unusable(h)) return -1;
-  if (h->box) return fail(h, (std::string("mdp_update_all: ") + kBoxOnly).c_str());
-  if (h->td3) return fail(h, "mdp_update_all: throughput mode is not supported with MATD3 (mdp_td3_enable)");
-  if (h->minimax) return fail(h, "mdp_update_all: throughput mode is not supported with M3DDPG (mdp_minimax_enable)");
-  if (h->approx)
-    return fail(h, "mdp_update_all: throughput mode is not supported with inferred policies (mdp_approx_enable)");
+  if (gate(h, Seam::UpdateAll)) return -1;
   if (h->update_mode != 1) return fail(h, "mdp_update_all: set throughput mode first");
   h->trained = true;
   if (h->len <= 0) return fail(h, "update on an empty replay buffer");
@@ -2931,27 +2956,10 @@ int mdp_update_all(mdp_handle* h, const int32_t* idx_dev, const float* u_tgt_dev
   return do_round_tp(h, idx, u_tgt_dev, u_act_dev, nullptr);
 }
 
-static const char* kMmNoPhase(const char* fn) {
-  static thread_local std::string m;
-  m = std::string(fn) + ": the phase entry points serve data parallelism; M3DDPG (mdp_minimax_enable) uses mdp_update";
-  return m.c_str();
-}
-
-static const char* kTd3NoPhase(const char* fn) {
-  static thread_local std::string m;
-  m = std::string(fn) + ": the phase entry points serve data parallelism; MATD3 (mdp_td3_enable) uses mdp_update";
-  return m.c_str();
-}
-
 int mdp_critic_grad(mdp_handle* h, int32_t agent, const int32_t* idx_dev, const float* u_tgt_dev) {
   if (bad_agent(h, agent)) return -1;
   if (!idx_dev) return fail(h, "critic_grad needs indices");
-  if (h->per) return fail(h, "mdp_critic_grad: the phase entry points serve data parallelism; prioritized replay uses mdp_update");
-  if (h->td3) return fail(h, kTd3NoPhase("mdp_critic_grad"));
-  if (h->minimax) return fail(h, kMmNoPhase("mdp_critic_grad"));
-  if (h->approx)
-    return fail(h, "mdp_critic_grad: the phase entry points serve data parallelism; inferred policies (mdp_approx_enable) use "
-                   "mdp_update");
+  if (gate(h, Seam::CriticGrad)) return -1;
   h->trained = true;
   MDP_DEV(h, idx_dev, 4 * (int64_t)h->cfg.batch_size, "mdp_critic_grad", false);
   MDP_DEV(h, u_tgt_dev, 4 * (int64_t)h->cfg.n_agents * h->cfg.batch_size * MDP_ACT_DIM, "mdp_critic_grad", true);
@@ -2961,11 +2969,7 @@ int mdp_critic_grad(mdp_handle* h, int32_t agent, const int32_t* idx_dev, const 
 int mdp_actor_grad(mdp_handle* h, int32_t agent, const int32_t* idx_dev, const float* u_act_dev) {
   if (bad_agent(h, agent)) return -1;
   if (!idx_dev) return fail(h, "actor_grad needs indices");
-  if (h->td3) return fail(h, kTd3NoPhase("mdp_actor_grad"));
-  if (h->minimax) return fail(h, kMmNoPhase("mdp_actor_grad"));
-  if (h->approx)
-    return fail(h, "mdp_actor_grad: the phase entry points serve data parallelism; inferred policies (mdp_approx_enable) use "
-                   "mdp_update");
+  if (gate(h, Seam::ActorGrad)) return -1;
   h->started = true;
   MDP_DEV(h, idx_dev, 4 * (int64_t)h->cfg.batch_size, "mdp_actor_grad", false);
   MDP_DEV(h, u_act_dev, 4 * (int64_t)h->cfg.batch_size * MDP_ACT_DIM, "mdp_actor_grad", true);
@@ -2974,21 +2978,13 @@ int mdp_actor_grad(mdp_handle* h, int32_t agent, const int32_t* idx_dev, const f
 
 int mdp_reduce_grad(mdp_handle* h, int32_t agent, int32_t net) {
   if (bad_agent(h, agent)) return -1;
-  if (h->td3) return fail(h, kTd3NoPhase("mdp_reduce_grad"));
-  if (h->minimax) return fail(h, kMmNoPhase("mdp_reduce_grad"));
-  if (h->approx)
-    return fail(h, "mdp_reduce_grad: the phase entry points serve data parallelism; inferred policies (mdp_approx_enable) use "
-                   "mdp_update");
+  if (gate(h, Seam::ReduceGrad)) return -1;
   return launch_reduce(h, opt_own(h, agent, net ? 1 : 0));
 }
 
 int mdp_apply_grad(mdp_handle* h, int32_t agent, int32_t net, float scale) {
   if (bad_agent(h, agent)) return -1;
-  if (h->td3) return fail(h, kTd3NoPhase("mdp_apply_grad"));
-  if (h->minimax) return fail(h, kMmNoPhase("mdp_apply_grad"));
-  if (h->approx)
-    return fail(h, "mdp_apply_grad: the phase entry points serve data parallelism; inferred policies (mdp_approx_enable) use "
-                   "mdp_update");
+  if (gate(h, Seam::ApplyGrad)) return -1;
   return launch_apply(h, opt_own(h, agent, net ? 1 : 0), scale);
 }
 
@@ -3186,7 +3182,7 @@ int mdp_evaluate_q(mdp_handle* h, int64_t first_episode, int32_t episodes, int32
   if (h->capturing || (hipStreamIsCapturing(h->stream, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone))
     return fail(h, "mdp_evaluate_q: the handle's stream is capturing a graph (evaluation is not captured)");
   (void)hipGetLastError();
-  const int n = h->cfg.n_agents, C = h->td3 ? 2 : 1;
+  const int n = h->cfg.n_agents, C = h->variant == Variant::Td3 ? 2 : 1;
   const int64_t en = 4 * (int64_t)episodes * n, ens = en * steps;
   MDP_DEV(h, u_dev, ens * MDP_ACT_DIM, fn, true);
   MDP_DEV(h, q_dev, ens * C, fn, false);
@@ -3207,7 +3203,7 @@ int mdp_evaluate_q(mdp_handle* h, int64_t first_episode, int32_t episodes, int32
   a.u_in = u_dev;
   a.ret = nullptr;
   a.bench = nullptr;
-  a.theta2 = h->td3 ? h->c2.theta : nullptr;
+  a.theta2 = h->variant == Variant::Td3 ? h->c2.theta : nullptr;
   a.steps = steps;
   a.ncrit = C;
   a.qin = lds_eval_q_in(h->L.topo);
@@ -3385,12 +3381,12 @@ int mdp_evaluate_matchups(mdp_handle* h, const float* bank_dev, int32_t n_sets, 
 // critical path for every round but the first
 static int step_launches(mdp_handle* h, int rounds) {
   const int nb = h->cfg.n_agents * h->cfg.batch_size;
-  if (h->per) {  // prioritized replay: no index prefetch in any launch
+  if (h->variant == Variant::Per) {  // prioritized replay: no index prefetch in any launch
     int rc = env_step_launch(h, nullptr, nullptr);
     for (int r = 0; r < rounds && !rc; ++r) rc = per_round_launches(h, r == 0);
     return rc;
   }
-  if (h->td3 || h->minimax || h->approx) {  // MATD3, M3DDPG, inferred policies: one n B draw per round, none rides on another launch
+  if (info(h).general_kernels) {  // MATD3, M3DDPG, inferred policies: one n B draw per round, none rides on another launch
     int rc = env_step_launch(h, nullptr, nullptr);
     for (int r = 0; r < rounds && !rc; ++r) {
       if ((rc = launch_make_index(h, nb, h->index))) break;
@@ -3612,11 +3608,11 @@ int mdp_check_finite(mdp_handle* h, int64_t* nonfinite) {
   HIPCHK(h, hipMemsetAsync(&h->ctl->nonfinite, 0, sizeof(uint32_t), h->stream));
   const float* sets[4] = {h->theta, h->target, h->m, h->v};
   for (const float* p : sets) HIPCHK(h, mdp_launch_count_nonfinite(p, h->L.PT, &h->ctl->nonfinite, h->stream));
-  if (h->td3) {  // the second critic's sets (actor spans of its regions stay zero)
+  if (h->variant == Variant::Td3) {  // the second critic's sets (actor spans of its regions stay zero)
     const float* twin[4] = {h->c2.theta, h->c2.target, h->c2.m, h->c2.v};
     for (const float* p : twin) HIPCHK(h, mdp_launch_count_nonfinite(p, h->L.PT, &h->ctl->nonfinite, h->stream));
   }
-  if (h->approx) {  // every observer's approximator sets (the spans without one stay zero)
+  if (h->variant == Variant::Approx) {  // every observer's approximator sets (the spans without one stay zero)
     for (int i = 0; i < h->cfg.n_agents; ++i)
       for (int k = MDP_APX_NET; k <= MDP_APX_V; ++k)
         HIPCHK(h, mdp_launch_count_nonfinite(apx_base(h, i, k), h->L.PT, &h->ctl->nonfinite, h->stream));
@@ -3668,17 +3664,7 @@ int64_t mdp_per_bytes(const mdp_config* cfg) {
 int mdp_per_enable(mdp_handle* h, void* buf_dev, int64_t bytes, float alpha, float beta0, float beta_inc, float eps,
                    float abs_err_upper) {
   MDP_NEED(h);
-  if (h->box) return fail(h, (std::string("mdp_per_enable: ") + kBoxOnly).c_str());
-  if (h->per) return fail(h, "mdp_per_enable: already enabled");
-  if (h->td3) return fail(h, "mdp_per_enable: prioritized replay and MATD3 (mdp_td3_enable) do not combine");
-  if (h->minimax) return fail(h, "mdp_per_enable: prioritized replay and M3DDPG (mdp_minimax_enable) do not combine");
-  if (h->approx)
-    return fail(h, "mdp_per_enable: prioritized replay and inferred policies (mdp_approx_enable) do not combine");
-  if (h->trained)
-    return fail(h, "mdp_per_enable: call it before the handle's first update or train call");
-  if (h->update_mode != 0)
-    return fail(h, "prioritized replay needs the strict update mode (throughput mode is not supported)");
-  if (h->comm || h->p2p || h->xbuf || h->cfg.world_size > 1) return fail(h, kPerNoDp);
+  if (gate(h, Seam::Enable, Variant::Per)) return -1;
   if (!(alpha >= 0.f) || !(beta0 >= 0.f && beta0 <= 1.f) || !(beta_inc >= 0.f) || !(eps >= 0.f) ||
       !(abs_err_upper > 0.f) || !std::isfinite(alpha) || !std::isfinite(beta_inc) || !std::isfinite(eps) ||
       !std::isfinite(abs_err_upper))
@@ -3709,11 +3695,10 @@ int mdp_per_enable(mdp_handle* h, void* buf_dev, int64_t bytes, float alpha, flo
   }
   HIPCHK(h, hipMemcpyAsync(h->per_st, st, sizeof(st), hipMemcpyHostToDevice, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
-  h->per = true;
-  destroy_graphs(h, true);  // graphs captured with the uniform draw
+  set_variant(h, Variant::Per);  // (drops the graphs captured with the uniform draw)
   // every filled row starts at the new-row priority; the cursor at the ring's present state
   if (per_sync(h, 0, true)) {
-    h->per = false;
+    h->variant = Variant::None;
     return -1;
   }
   return 0;
@@ -3729,33 +3714,14 @@ int64_t mdp_td3_bytes(const mdp_config* cfg) {
 
 int mdp_td3_enable(mdp_handle* h, void* buf_dev, int64_t bytes, int32_t policy_delay) {
   MDP_NEED(h);
-  if (h->box) return fail(h, (std::string("mdp_td3_enable: ") + kBoxOnly).c_str());
-  if (h->td3) return fail(h, "mdp_td3_enable: already enabled");
-  if (h->trained) return fail(h, "mdp_td3_enable: call it before the handle's first update, round or train call");
+  if (gate(h, Seam::Enable, Variant::Td3)) return -1;
   if (policy_delay < 1 || policy_delay > 8) return fail(h, "mdp_td3_enable: policy_delay must be in 1..8");
-  if (h->per) return fail(h, "mdp_td3_enable: MATD3 and prioritized replay (mdp_per_enable) do not combine");
-  if (h->minimax) return fail(h, "mdp_td3_enable: MATD3 and M3DDPG (mdp_minimax_enable) do not combine");
-  if (h->approx) return fail(h, "mdp_td3_enable: MATD3 and inferred policies (mdp_approx_enable) do not combine");
-  if (h->update_mode != 0)
-    return fail(h, "mdp_td3_enable: MATD3 needs the strict update mode (throughput mode is not supported)");
-  if (h->comm || h->p2p || h->xbuf || h->cfg.world_size > 1)
-    return fail(h, (std::string("mdp_td3_enable: ") + kTd3NoDp).c_str());
   const Td3Layout tl = td3_layout(h->cfg, h->L);
-  if (!buf_dev) return fail(h, "mdp_td3_enable: buf_dev is null");
-  if (bytes < tl.total) return fail(h, "mdp_td3_enable: bytes is smaller than mdp_td3_bytes");
   if (lds_critic_twin_bytes(h->L.topo, 1) > MDP_LDS_BUDGET)
     return fail(h, "mdp_td3_enable: the twin critic step does not fit the kernels' LDS envelope");
-  MDP_DEV(h, buf_dev, tl.total, "mdp_td3_enable", false);
   char* b = (char*)buf_dev;
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  HIPCHK(h, hipMemsetAsync(b, 0, tl.total, h->stream));
-  std::vector<float> beta(4 * (size_t)h->cfg.n_agents);
-  for (int i = 0; i < h->cfg.n_agents; ++i) {  // as mdp_create: the powers start at beta
-    beta[4 * i] = beta[4 * i + 2] = h->cfg.adam_b1;
-    beta[4 * i + 1] = beta[4 * i + 3] = h->cfg.adam_b2;
-  }
-  HIPCHK(h, hipMemcpyAsync(b + tl.beta, beta.data(), 4 * beta.size(), hipMemcpyHostToDevice, h->stream));
-  HIPCHK(h, hipStreamSynchronize(h->stream));
+  if (take_side_buffer(h, "mdp_td3_enable", "mdp_td3_bytes", b, bytes, tl.total)) return -1;
+  if (write_beta_powers(h, (float*)(b + tl.beta), h->cfg.n_agents)) return -1;
   mdp_handle::Critic2& c = h->c2;
   c.theta = (float*)(b + tl.theta);
   c.target = (float*)(b + tl.target);
@@ -3766,20 +3732,16 @@ int mdp_td3_enable(mdp_handle* h, void* buf_dev, int64_t bytes, int32_t policy_d
   c.stat = (double*)(b + tl.stat);
   c.beta = (float*)(b + tl.beta);
   c.stats = (double*)(b + tl.stats);
-  c.ticket = (uint32_t*)(b + tl.ticket);
-  c.ctr = (uint32_t*)(b + tl.ctr);
-  c.part = (uint64_t*)(b + tl.part);
+  c.sync = sync_bind(b, tl.sync);
   h->td3_delay = policy_delay;
   for (int i = 0; i < MDP_MAX_AGENTS; ++i) h->td3_count[i] = h->td3_work[i] = 0;
-  h->td3 = true;
-  h->general_grads = true;  // MATD3 runs on the general kernels: no actor_pre / critic_pre, no index prefetch
-  destroy_graphs(h, true);
+  set_variant(h, Variant::Td3);
   return 0;
 }
 
 int mdp_td3_info(mdp_handle* h, int32_t agent, double out4[4]) {
   if (bad_agent(h, agent)) return -1;
-  if (!h->td3) return fail(h, "mdp_td3_info: MATD3 is not enabled (mdp_td3_enable)");
+  if (need_variant(h, "mdp_td3_info", Variant::Td3)) return -1;
   if (!out4) return fail(h, "mdp_td3_info: out4 is null");
   double q1 = 0.0, q2 = 0.0;
   HIPCHK(h, hipMemcpyAsync(&q1, h->stats + agent * 8, 8, hipMemcpyDeviceToHost, h->stream));
@@ -3795,23 +3757,12 @@ int mdp_td3_info(mdp_handle* h, int32_t agent, double out4[4]) {
 // ----------------------------------------------------------------- M3DDPG
 int mdp_minimax_enable(mdp_handle* h, const float* eps_host) {
   MDP_NEED(h);
-  if (h->box) return fail(h, (std::string("mdp_minimax_enable: ") + kBoxOnly).c_str());
-  if (h->minimax) return fail(h, "mdp_minimax_enable: already enabled");
-  if (h->trained)
-    return fail(h, "mdp_minimax_enable: call it before the handle's first update, round or train call");
+  if (gate(h, Seam::Enable, Variant::Minimax)) return -1;
   if (!eps_host) return fail(h, "mdp_minimax_enable: eps_host is null");
   const int n = h->cfg.n_agents;
   for (int k = 0; k < n * n; ++k)
     if (!std::isfinite(eps_host[k]) || eps_host[k] < 0.f)
       return fail(h, "mdp_minimax_enable: eps_host must hold finite values >= 0");
-  if (h->per) return fail(h, "mdp_minimax_enable: M3DDPG and prioritized replay (mdp_per_enable) do not combine");
-  if (h->td3) return fail(h, "mdp_minimax_enable: M3DDPG and MATD3 (mdp_td3_enable) do not combine");
-  if (h->approx)
-    return fail(h, "mdp_minimax_enable: M3DDPG and inferred policies (mdp_approx_enable) do not combine");
-  if (h->update_mode != 0)
-    return fail(h, "mdp_minimax_enable: M3DDPG needs the strict update mode (throughput mode is not supported)");
-  if (h->comm || h->p2p || h->xbuf || h->cfg.world_size > 1)
-    return fail(h, (std::string("mdp_minimax_enable: ") + kMmNoDp).c_str());
   const Topo& T = h->L.topo;
   if (T.H != 64 && T.H != 128 && T.H != 256)
     return fail(h, "mdp_minimax_enable: the gradient kernels serve num_units 64, 128 or 256");
@@ -3824,15 +3775,13 @@ int mdp_minimax_enable(mdp_handle* h, const float* eps_host) {
   HIPCHK(h, hipStreamSynchronize(h->stream));
   for (int i = 0; i < MDP_MAX_AGENTS; ++i)
     for (int j = 0; j < MDP_MAX_AGENTS; ++j) h->mm_eps[i][j] = (i < n && j < n && i != j) ? eps_host[i * n + j] : 0.f;
-  h->minimax = true;
-  h->general_grads = true;  // M3DDPG runs on the general kernels: no actor_pre / critic_pre, no index prefetch
-  destroy_graphs(h, true);
+  set_variant(h, Variant::Minimax);
   return 0;
 }
 
 int mdp_minimax_info(mdp_handle* h, float* eps_out_host) {
   MDP_NEED(h);
-  if (!h->minimax) return fail(h, "mdp_minimax_info: M3DDPG is not enabled (mdp_minimax_enable)");
+  if (need_variant(h, "mdp_minimax_info", Variant::Minimax)) return -1;
   if (!eps_out_host) return fail(h, "mdp_minimax_info: eps_out_host is null");
   const int n = h->cfg.n_agents;
   for (int i = 0; i < n; ++i)
@@ -3842,7 +3791,7 @@ int mdp_minimax_info(mdp_handle* h, float* eps_out_host) {
 
 int mdp_minimax_debug_adv(mdp_handle* h, float* critic_adv_dev, float* actor_adv_dev) {
   MDP_NEED(h);
-  if (!h->minimax) return fail(h, "mdp_minimax_debug_adv: M3DDPG is not enabled (mdp_minimax_enable)");
+  if (need_variant(h, "mdp_minimax_debug_adv", Variant::Minimax)) return -1;
   const int64_t bytes = 4 * (int64_t)h->cfg.batch_size * h->cfg.n_agents * MDP_ACT_DIM;
   if (need_dev(h, critic_adv_dev, bytes, "mdp_minimax_debug_adv", "critic_adv_dev", true)) return -1;
   if (need_dev(h, actor_adv_dev, bytes, "mdp_minimax_debug_adv", "actor_adv_dev", true)) return -1;
@@ -3863,41 +3812,18 @@ int64_t mdp_approx_bytes(const mdp_config* cfg) {
 
 int mdp_approx_enable(mdp_handle* h, void* buf_dev, int64_t bytes, float lambda) {
   MDP_NEED(h);
-  if (h->box) return fail(h, (std::string("mdp_approx_enable: ") + kBoxOnly).c_str());
-  if (h->approx) return fail(h, "mdp_approx_enable: already enabled");
-  if (h->trained)
-    return fail(h, "mdp_approx_enable: call it before the handle's first update, round or train call");
+  if (gate(h, Seam::Enable, Variant::Approx)) return -1;
   if (!std::isfinite(lambda) || lambda < 0.f) return fail(h, "mdp_approx_enable: lambda must be finite and >= 0");
-  if (h->per)
-    return fail(h, "mdp_approx_enable: inferred policies and prioritized replay (mdp_per_enable) do not combine");
-  if (h->td3) return fail(h, "mdp_approx_enable: inferred policies and MATD3 (mdp_td3_enable) do not combine");
-  if (h->minimax)
-    return fail(h, "mdp_approx_enable: inferred policies and M3DDPG (mdp_minimax_enable) do not combine");
-  if (h->update_mode != 0)
-    return fail(h, "mdp_approx_enable: inferred policies need the strict update mode (throughput mode is not "
-                   "supported)");
-  if (h->comm || h->p2p || h->xbuf || h->cfg.world_size > 1)
-    return fail(h, (std::string("mdp_approx_enable: ") + kApxNoDp).c_str());
   const Topo& T = h->L.topo;
   if (T.H != 64 && T.H != 128 && T.H != 256)
     return fail(h, "mdp_approx_enable: the gradient kernels serve num_units 64, 128 or 256");
   if (lds_approx_bytes(T) > MDP_LDS_BUDGET)
     return fail(h, "mdp_approx_enable: the approximator step does not fit the kernels' LDS envelope");
   const ApxLayout al = apx_layout(h->cfg, h->L);
-  if (!buf_dev) return fail(h, "mdp_approx_enable: buf_dev is null");
-  if (bytes < al.total) return fail(h, "mdp_approx_enable: bytes is smaller than mdp_approx_bytes");
-  MDP_DEV(h, buf_dev, al.total, "mdp_approx_enable", false);
   char* b = (char*)buf_dev;
   const int n = h->cfg.n_agents;
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  HIPCHK(h, hipMemsetAsync(b, 0, al.total, h->stream));
-  std::vector<float> beta(4 * (size_t)n * n);
-  for (int q = 0; q < n * n; ++q) {  // as mdp_create: the powers start at beta
-    beta[4 * q] = beta[4 * q + 2] = h->cfg.adam_b1;
-    beta[4 * q + 1] = beta[4 * q + 3] = h->cfg.adam_b2;
-  }
-  HIPCHK(h, hipMemcpyAsync(b + al.beta, beta.data(), 4 * beta.size(), hipMemcpyHostToDevice, h->stream));
-  HIPCHK(h, hipStreamSynchronize(h->stream));
+  if (take_side_buffer(h, "mdp_approx_enable", "mdp_approx_bytes", b, bytes, al.total)) return -1;
+  if (write_beta_powers(h, (float*)(b + al.beta), n * n)) return -1;
   mdp_handle::Approx& x = h->apx;
   x.buf = b;
   x.region = al.region;
@@ -3905,23 +3831,19 @@ int mdp_approx_enable(mdp_handle* h, void* buf_dev, int64_t bytes, float lambda)
   x.slab = (float*)(b + al.slab);
   x.stat = (double*)(b + al.stat);
   x.beta = (float*)(b + al.beta);
-  x.ticket = (uint32_t*)(b + al.ticket);
-  x.ctr = (uint32_t*)(b + al.ctr);
-  x.part = (uint64_t*)(b + al.part);
+  x.sync = sync_bind(b, al.sync);
   h->apx_lambda = lambda;
   for (int i = 0; i < MDP_MAX_AGENTS; ++i) h->apx_count[i] = 0;
   h->apx_pending = -1;
-  h->approx = true;
-  h->general_grads = true;  // runs on the general kernels: no actor_pre / critic_pre, no index prefetch
-  destroy_graphs(h, true);
+  set_variant(h, Variant::Approx);
   return 0;
 }
 
 // the pair (observer, agent) of an approximator entry point `fn` (agent -1: any), or the refusal
 static int need_apx(mdp_handle* h, int32_t observer, int32_t agent, const char* fn) {
   if (unusable(h)) return -1;
+  if (need_variant(h, fn, Variant::Approx)) return -1;
   const std::string f(fn);
-  if (!h->approx) return fail(h, (f + ": inferred policies are not enabled (mdp_approx_enable)").c_str());
   const int n = h->cfg.n_agents;
   if (observer < 0 || observer >= n) return fail(h, (f + ": observer out of range").c_str());
   if (h->L.topo.ag[observer].local_q)
@@ -4039,7 +3961,7 @@ int mdp_approx_step(mdp_handle* h, int32_t observer, const int32_t* idx_dev) {
 
 static int need_per(mdp_handle* h, int32_t agent, const char* fn) {
   if (bad_agent(h, agent)) return -1;
-  if (!h->per) return fail(h, (std::string(fn) + ": prioritized replay is not enabled (mdp_per_enable)").c_str());
+  if (need_variant(h, fn, Variant::Per)) return -1;
   return 0;
 }
 
@@ -4077,7 +3999,7 @@ int mdp_per_update_errors(mdp_handle* h, int32_t agent, const int32_t* pos_dev, 
   return per_write(h, agent, pos_dev, abs_err_dev, count, true, "mdp_per_update_errors");
 }
 
-int64_t mdp_per_tree_nodes(const mdp_handle* h) { return (unusable(h) || !h->per) ? -1 : 2 * h->per_P; }
+int64_t mdp_per_tree_nodes(const mdp_handle* h) { return (unusable(h) || h->variant != Variant::Per) ? -1 : 2 * h->per_P; }
 
 int mdp_per_slots(mdp_handle* h, int32_t agent, int64_t out3[3]) {
   if (need_per(h, agent, "mdp_per_slots")) return -1;

@@ -13,7 +13,7 @@ import os
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, variants
 from ._lib import MdpConfig, MdpTensorInfo
 
 TENSOR_NAMES = ("W1", "b1", "W2", "b2", "W3", "b3")
@@ -87,6 +87,15 @@ class Engine:
         (actor_logits) is [mean | logstd], 2 act_dims[i] wide.  With a scenario,
         act_dims may be None: a box agent is Box(2), the others keep their own
         space.  Strict mode, one GPU, none of prioritized / td3 / minimax / approx."""
+        # one variant per handle, on one GPU (variants.py): refused here, before
+        # anything is allocated or created on the device
+        minimax = bool(minimax) or minimax_eps is not None
+        why = variants.engine_refusal(dict(prioritized=prioritized, td3=td3, minimax=minimax, approx=approx),
+                                      int(world_size))
+        if why:
+            raise _lib.MdpError(why)
+        if approx and not (np.isfinite(float(approx_lambda)) and float(approx_lambda) >= 0):
+            raise _lib.MdpError(f"approx_lambda must be finite and >= 0, got {approx_lambda!r}")
         self.lib = _lib.load()
         if not torch.cuda.is_available():
             raise RuntimeError("maddpg_amd runs on a ROCm GPU only (no CPU fallback)")
@@ -107,13 +116,6 @@ class Engine:
         self.approx = bool(approx)
         self.approx_lambda = float(approx_lambda)
         self.approx_buf = None
-        if self.approx:     # refused here, before anything is allocated or created on the device
-            other = [k for k, on in (("prioritized", prioritized), ("td3", td3),
-                                     ("minimax", minimax or minimax_eps is not None),
-                                     ("world_size > 1", self.world_size > 1)) if on]
-            if other or not (np.isfinite(self.approx_lambda) and self.approx_lambda >= 0):
-                raise _lib.MdpError(f"approx does not combine with {', '.join(other)} (mdp_approx_enable)" if other
-                                    else f"approx_lambda must be finite and >= 0, got {approx_lambda!r}")
         cfg = MdpConfig()
         cfg.n_agents = n
         for i in range(n):
@@ -205,14 +207,8 @@ class Engine:
         self.td3 = bool(td3)
         self.policy_delay = int(policy_delay)
         self.td3_buf = None
-        if self.prioritized and self.td3:
-            self.close()
-            raise _lib.MdpError("td3 and prioritized replay do not combine (mdp_td3_enable)")
-        self.minimax = bool(minimax) or minimax_eps is not None
+        self.minimax = minimax
         self.minimax_eps = None
-        if self.minimax and (self.prioritized or self.td3):
-            self.close()
-            raise _lib.MdpError("minimax combines with neither prioritized replay nor td3 (mdp_minimax_enable)")
         if self.prioritized:
             self._per_enable(per_alpha, per_beta0, per_beta_inc, per_eps, per_abs_err_upper)
         if self.td3:
@@ -510,12 +506,10 @@ class Engine:
         tf.train.Saver().save(sess, fname) writes it (tf_util.py:267-273;
         `fname`.index + `fname`.data-00000-of-00001 + the `checkpoint` state
         file; no .meta -- the graph is built by code on both sides)."""
-        if fmt == "tf1" and self.td3:
-            raise ValueError("save_state(fmt='tf1') on a TD3 engine: the second critic has no reference variable "
-                             "names; save as npz")
-        if fmt == "tf1" and self.approx:
-            raise ValueError("save_state(fmt='tf1') on an approx engine: the approximators have no reference variable "
-                             "names; save as npz")
+        for r in variants.VARIANTS:
+            if fmt == "tf1" and r.npz_only and getattr(self, r.kw):
+                raise ValueError(f"save_state(fmt='tf1') on an engine with {r.name} ({r.kw}): its state has no "
+                                 "reference variable names; save as npz")
         if fmt == "tf1":
             from .common import tf_checkpoint as tfc
             self._drop_stale(fname, keep="tf1")

@@ -11,7 +11,7 @@ applies unchanged.  Index draws, gathers, both optimiser steps and Polyak
 updates run on the device in the reference's agent order.
 """
 import os
-from . import envs
+from . import envs, variants
 from .engine import Engine
 from .parallel import EngineOps, make_allreduce, strict_round, throughput_round
 
@@ -49,14 +49,10 @@ class VecRunner:
                  per_beta_inc=0.001, per_eps=0.01, per_abs_err_upper=1.0, td3=False, policy_delay=2,
                  minimax=False, adv_eps=1e-3, adv_eps_s=1e-5, approx=False, approx_lambda=1e-3,
                  continuous=False):
-        if continuous and world_size > 1:
-            raise ValueError("--continuous-actions runs on one GPU (Box action spaces have no data-parallel variant)")
-        if td3 and world_size > 1:
-            raise ValueError("--td3 runs on one GPU (MATD3 has no data-parallel variant)")
-        if minimax and world_size > 1:
-            raise ValueError("--minimax runs on one GPU (M3DDPG has no data-parallel variant)")
-        if approx and world_size > 1:
-            raise ValueError("--approx-policies runs on one GPU (inferred policies have no data-parallel variant)")
+        why = variants.runner_refusal(dict(prioritized=prioritized, td3=td3, minimax=minimax, approx=approx,
+                                           continuous=continuous), world_size)
+        if why:
+            raise ValueError(why)
         sp = envs.spec(scenario, n_agents, scenario_adversaries, continuous=continuous)
         self.spec = sp
         n = sp.n_agents

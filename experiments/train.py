@@ -118,6 +118,10 @@ def parse_args(argv=None):
                         help="Box action spaces: every agent that moves and does not speak gets a Box(2) space and a "
                              "diagonal-Gaussian policy, its action the force itself (strict mode, one GPU; not with "
                              "--prioritized-replay, --td3, --minimax or --approx-policies)")
+    parser.add_argument("--action-squash", choices=("none", "tanh"), default="none",
+                        help="--continuous-actions: tanh puts every Box agent's sample through tanh, an action "
+                             "inside [-1, 1] (the force a * accel is then bounded, as a Discrete(5) agent's is). "
+                             "npz checkpoints record it; with a TF1 bundle give the flag again on restore")
     parser.add_argument("--approx-lambda", type=float, default=1e-3,
                         help="--approx-policies: weight of the approximators' entropy regulariser")
     # device-side policy evaluation (whole episodes in one launch; training state untouched)
@@ -436,7 +440,9 @@ def td3_flags(arglist, world=1):
 
 
 def continuous_flags(arglist, world=1):
-    """--continuous-actions is Box spaces"""
+    """--continuous-actions is Box spaces; --action-squash is a setting of theirs"""
+    if getattr(arglist, "action_squash", "none") != "none" and not getattr(arglist, "continuous_actions", False):
+        raise SystemExit("--action-squash needs --continuous-actions")
     _combination("--continuous-actions", arglist, world)
 
 
@@ -475,6 +481,7 @@ def _make_runner(arglist, VecRunner, world, rank, per):
                        # the learning-curve windows of one terminal step span <= save_rate + E episodes
                        episode_log_rows=max(4096, 4 * arglist.num_envs, arglist.save_rate + 2 * arglist.num_envs),
                        continuous=getattr(arglist, "continuous_actions", False),
+                       squash=getattr(arglist, "action_squash", "none"),
                        **per, **td3_kwargs(arglist), **minimax_kwargs(arglist), **approx_kwargs(arglist))
     if arglist.update_mode != "strict":
         runner.eng.set_update_mode(arglist.update_mode)

@@ -175,6 +175,25 @@ int mdp_get_act_dims(const mdp_handle* h, int32_t dims[MDP_MAX_AGENTS]);
 int mdp_set_act_spaces(mdp_handle* h, const int32_t kinds[MDP_MAX_AGENTS], const int32_t dims[MDP_MAX_AGENTS]);
 /* the kinds and widths in use (0 beyond n_agents); either pointer may be NULL */
 int mdp_get_act_spaces(const mdp_handle* h, int32_t kinds[MDP_MAX_AGENTS], int32_t dims[MDP_MAX_AGENTS]);
+/* A Box agent's squash: MDP_SQUASH_NONE, the policy above, or MDP_SQUASH_TANH, a
+ * bounded action.  The sample z = mean + exp(logstd) * eps is formed as above and the
+ * action is a_k = tanhf(z_k), inside [-1, 1]: what the agent plays, what replay
+ * stores and what the critics see.  The backward through the sample is dz_k =
+ * da_k * (1 - a_k * a_k), dmean_k = dz_k, dlogstd_k = dz_k * std_k * eps_k; the head,
+ * its width, the noise and the regulariser mean(square(flat)) are unchanged, and so
+ * is every layout.  MDP_EVAL_MEAN plays tanh(mean).  The bounds are fixed at
+ * [-1, 1]; a device scenario takes a * accel as the force, the magnitude a
+ * Discrete(5) agent can reach.  No clamp on logstd.
+ * squash[i] is one of the two values for each of the n_agents agents; a non-zero
+ * entry for a Discrete agent, an unknown value and a null pointer are refused with
+ * a message.  Accepted when mdp_set_act_spaces is, after it: mdp_set_act_spaces and
+ * mdp_set_act_dims reset every squash to none.  A squashed handle is a Box handle in
+ * everything else (mdp_get_act_spaces says MDP_ACT_BOX; the same refusals). */
+#define MDP_SQUASH_NONE 0
+#define MDP_SQUASH_TANH 1
+int mdp_set_act_squash(mdp_handle* h, const int32_t squash[MDP_MAX_AGENTS]);
+/* the squashes in use (0 beyond n_agents and for a Discrete agent) */
+int mdp_get_act_squash(const mdp_handle* h, int32_t squash[MDP_MAX_AGENTS]);
 
 /* ---- parameters (golden injection, checkpoint; tf_util.py:259-273) --- */
 int mdp_set_params(mdp_handle* h, int32_t agent, int32_t which, const float* src_host, int64_t n);

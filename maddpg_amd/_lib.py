@@ -20,6 +20,7 @@ HEADER = os.path.join(os.path.dirname(HERE), "include", "maddpg_hip.h")
 
 MAX_AGENTS = 8
 ACT_DISCRETE, ACT_BOX = 0, 1   # MDP_ACT_DISCRETE / MDP_ACT_BOX (mdp_set_act_spaces)
+SQUASH_NONE, SQUASH_TANH = 0, 1   # MDP_SQUASH_NONE / MDP_SQUASH_TANH (mdp_set_act_squash)
 ACT_DIM = 5   # MDP_ACT_DIM: the widest action space, and the width of every device action slot
 BENCH_W = 8   # MDP_BENCH_W: floats per agent benchmark_data record
 MAX_UNITS = 256  # MDP_MAX_UNITS: largest --num-units
@@ -107,6 +108,8 @@ SIGNATURES = {
     "mdp_get_act_dims": (ctypes.c_int, [_P, _I32P]),
     "mdp_set_act_spaces": (ctypes.c_int, [_P, _I32P, _I32P]),
     "mdp_get_act_spaces": (ctypes.c_int, [_P, _I32P, _I32P]),
+    "mdp_set_act_squash": (ctypes.c_int, [_P, _I32P]),
+    "mdp_get_act_squash": (ctypes.c_int, [_P, _I32P]),
     "mdp_set_params": (ctypes.c_int, [_P, _I32, _I32, _F32P, _I64]),
     "mdp_get_params": (ctypes.c_int, [_P, _I32, _I32, _F32P, _I64]),
     "mdp_get_beta_powers": (ctypes.c_int, [_P, _I32, _I32, _F32P]),

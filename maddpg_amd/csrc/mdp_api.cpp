@@ -2303,6 +2303,34 @@ int mdp_get_act_spaces(const mdp_handle* h, int32_t kinds[MDP_MAX_AGENTS], int32
   return 0;
 }
 
+// a Box agent's squash: one bit of its nibble of Topo::act_w4, which every
+// sampler site already receives.  A squashed handle is a Box handle to the
+// gate (h->box is unchanged), so nothing else on the host knows of it.
+// (mdp_set_act_dims / mdp_set_act_spaces rewrite the nibbles: squash none.)
+int mdp_set_act_squash(mdp_handle* h, const int32_t squash[MDP_MAX_AGENTS]) {
+  MDP_NEED(h);
+  if (!squash) return fail(h, "mdp_set_act_squash: squash is null");
+  if (h->started || h->trained)
+    return fail(h, "mdp_set_act_squash: call it before the handle's first parameter write, act, update or env call");
+  const int n = h->cfg.n_agents;
+  for (int i = 0; i < n; ++i) {
+    if (squash[i] != MDP_SQUASH_NONE && squash[i] != MDP_SQUASH_TANH)
+      return fail(h, "mdp_set_act_squash: unknown squash (MDP_SQUASH_NONE, MDP_SQUASH_TANH)");
+    if (squash[i] != MDP_SQUASH_NONE && !topo_act_box(h->L.topo, i))
+      return fail(h, "mdp_set_act_squash: only a Box agent (mdp_set_act_spaces) may carry a squash");
+  }
+  for (int i = 0; i < n; ++i)
+    if (topo_act_box(h->L.topo, i)) topo_set_act_squash(h->L.topo, i, squash[i] == MDP_SQUASH_TANH);
+  return 0;
+}
+
+int mdp_get_act_squash(const mdp_handle* h, int32_t squash[MDP_MAX_AGENTS]) {
+  if (unusable(h) || !squash) return -1;
+  for (int i = 0; i < MDP_MAX_AGENTS; ++i)
+    squash[i] = i < h->cfg.n_agents && topo_act_squash(h->L.topo, i) ? MDP_SQUASH_TANH : MDP_SQUASH_NONE;
+  return 0;
+}
+
 int mdp_get_act_dims(const mdp_handle* h, int32_t dims[MDP_MAX_AGENTS]) {
   if (unusable(h) || !dims) return -1;
   for (int i = 0; i < MDP_MAX_AGENTS; ++i) dims[i] = i < h->cfg.n_agents ? topo_act_w(h->L.topo, i) : 0;

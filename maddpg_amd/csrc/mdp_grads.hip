@@ -379,7 +379,7 @@ __device__ __forceinline__ void mm_perturb(const Topo& T, int self, const float*
     float* xa = X + row * ldx + a0 + MDP_ACT_DIM * j;
     if (j != self) {
       const float* g = dxa + row * lda + MDP_ACT_DIM * j;
-      const int kj = topo_act_w(T, j);
+      const int kj = topo_act_w7(T, j);  // (M3DDPG refuses Box: every agent is Discrete)
       float ss = 0.f;
       for (int k = 0; k < kj; ++k) ss = ss + g[k] * g[k];
       const float inv = 1.0f / sqrtf(fmaxf(ss, 1e-12f));
@@ -463,7 +463,8 @@ __device__ __forceinline__ void critic_backward(const float* th, const NDesc& nd
 // APX (A = CriticArgsApx): inferred policies -- the target action of every agent
 // j != agent comes from this agent's target approximator of j (a.apx_target,
 // agent j's actor span) instead of target actor j; MADDPG critics
-template <int H, bool PER = false, class A = CriticArgs, bool TWIN = false, bool MM = false, bool APX = false>
+template <int H, bool PER = false, class A = CriticArgs, bool TWIN = false, bool MM = false, bool APX = false,
+          bool SQ = false>
 __device__ __forceinline__ void critic_body(const A& a, const Topo& T, const int blk) {
   static_assert(!(MM && (TWIN || PER)), "minimax combines with neither twin critics nor prioritized replay");
   static_assert(!(APX && (MM || TWIN || PER)), "inferred policies combine with none of the other options");
@@ -666,7 +667,7 @@ __device__ __forceinline__ void critic_body(const A& a, const Topo& T, const int
       } else {
         uniforms5(a.seed, (uint32_t)((a.agent << 8) | (j + 1)), ctr, (uint32_t)(r0 + row), u);
       }
-      policy_sample(lg + jb * MDP_R * 8 + row * 8, u, act, topo_act_space(T, j));
+      policy_sample<SQ>(lg + jb * MDP_R * 8 + row * 8, u, act, topo_act_space(T, j));
       const int dst = lq ? ag.obs_dim : T.sum_obs + MDP_ACT_DIM * j;
       for (int k = 0; k < MDP_ACT_DIM; ++k) xt[row * ldc + dst + k] = act[k];
     }
@@ -854,7 +855,9 @@ __device__ __forceinline__ void critic_body(const A& a, const Topo& T, const int
 // APX: the inferred-policies twin (A = CriticArgsApx), strict mode only
 template <int H, bool PER = false, class A = CriticArgs, bool TWIN = false, bool MM = false, bool APX = false>
 __global__ __launch_bounds__(MDP_GEN_THREADS) void k_critic_grad(A a) {
-  critic_body<H, PER, A, TWIN, MM, APX>(a, a.topo, blockIdx.x);
+  // (A = CriticArgsSq: a handle with a squashed Box agent, DESIGN 26 -- the target
+  // actors' samples go through tanh where the agent's squash bit says so)
+  critic_body<H, PER, A, TWIN, MM, APX, std::is_same<A, CriticArgsSq>::value>(a, a.topo, blockIdx.x);
 }
 
 // AA: ActorArgs, or the Topo-less ActorArgsHead of a gradient-pair launch
@@ -862,7 +865,7 @@ __global__ __launch_bounds__(MDP_GEN_THREADS) void k_critic_grad(A a) {
 // backward to the other agents' replayed actions, those moved against Q (a
 // constant of the backward), the critic again on the moved input, and the
 // step's backward from there
-template <int H, class AA, bool MM = false>
+template <int H, class AA, bool MM = false, bool SQ = false>
 __device__ __forceinline__ void actor_body(const AA& a, const Topo& T, const int blk) {
   constexpr int NT = H / 16;
   extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -959,7 +962,7 @@ __device__ __forceinline__ void actor_body(const AA& a, const Topo& T, const int
         uniforms5(a.seed, (uint32_t)((a.agent << 8) | 0x80), ctr, (uint32_t)(r0 + lane), u);
       }
       // (a Box agent: std * eps, the backward's factor, behind the slot's 5 entries)
-      policy_sample(lg + lane * 8, u, av + lane * 8, topo_act_space(T, a.agent), av + lane * 8 + MDP_ACT_DIM);
+      policy_sample<SQ>(lg + lane * 8, u, av + lane * 8, topo_act_space(T, a.agent), av + lane * 8 + MDP_ACT_DIM);
       if (!par)
         for (int k = 0; k < MDP_ACT_DIM; ++k) x[lane * ldc + ag.a_in_off + k] = av[lane * 8 + k];
     }
@@ -1103,11 +1106,13 @@ __device__ __forceinline__ void actor_body(const AA& a, const Topo& T, const int
     // softmax backward + regulariser: dlogits = (da - sum(a*da)) * a + reg*2*p/(B*A); loss partials
     double s_q = 0.0, s_p = 0.0;
     if (lane < MDP_R) {
-      const int aw = topo_head_w(T, a.agent);
+      const int aw = SQ ? topo_head_w(T, a.agent) : topo_head_w7(T, a.agent);
       const float reg_scale = __builtin_expect(aw == MDP_ACT_DIM, 1) ? a.reg_scale : T.reg_scale_w[aw - 1];
       if (__builtin_expect(topo_act_box(T, a.agent), 0)) {  // Gaussian head: dmean | dlogstd
         float g[MDP_ACT_DIM];
-        gauss_backward(lg + lane * 8, da + lane * 8, av + lane * 8 + MDP_ACT_DIM, aw >> 1, reg_scale, g);
+        // (a squashed agent: 1 - a^2 from the sample in the tile's first lanes)
+        gauss_backward<SQ>(lg + lane * 8, da + lane * 8, av + lane * 8 + MDP_ACT_DIM, aw >> 1, reg_scale, g,
+                           SQ && topo_act_squash(T, a.agent) ? av + lane * 8 : nullptr);
         for (int k = 0; k < MDP_ACT_DIM; ++k) dl[lane * 8 + k] = lane < nvalid ? g[k] : 0.f;
       } else {
         float dot = 0.f;
@@ -1177,7 +1182,7 @@ __global__ __launch_bounds__(MDP_GEN_THREADS) void k_actor_grad(AA a) {
     MDP_KARG_TOUCH("s"(a.agent), "s"(a.slab_stride), "s"(a.cpre_agent), "s"(a.topo.n));
     MDP_KARG_TOUCH(MDP_KARG_ADESC(a.topo.ag[a.agent]));
   }
-  actor_body<H, AA, MM>(a, a.topo, blockIdx.x);
+  actor_body<H, AA, MM, std::is_same<AA, ActorArgsSq>::value>(a, a.topo, blockIdx.x);  // (as k_critic_grad)
 }
 
 // Inferred policies: one gradient step's raw gradients of the
@@ -1227,7 +1232,7 @@ __global__ __launch_bounds__(4 * H) void k_approx_grad(ApproxArgs a) {
     wave_sync();
     double s_ce = 0.0, s_en = 0.0;
     if (lane < MDP_R) {
-      const int A = topo_act_w(T, j);
+      const int A = topo_act_w7(T, j);  // (inferred policies refuse Box: every agent is Discrete)
       const float* l = lg + lane * 8;
       const float* ac = av + lane * 8;
       float mx = l[0];
@@ -1323,6 +1328,11 @@ hipError_t mdp_launch_grad_pair(const GradPairArgs& a, int H, int lds_bytes, hip
 }
 hipError_t mdp_launch_critic_grad(const CriticArgs& a, int H, int lds_bytes, hipStream_t s) {
   return mdp_for_width(H, [&](auto h) {
+    if (__builtin_expect(topo_any_squash(a.topo), 0)) {
+      CriticArgsSq q;
+      static_cast<CriticArgs&>(q) = a;
+      return launch_gen<k_critic_grad<h.value, false, CriticArgsSq>>(row_tiles(a.B), lds_bytes, s, q);
+    }
     return launch_gen<k_critic_grad<h.value>>(row_tiles(a.B), lds_bytes, s, a);
   });
 }
@@ -1359,6 +1369,11 @@ hipError_t mdp_launch_approx_grad(const ApproxArgs& a, int H, int lds_bytes, hip
 }
 hipError_t mdp_launch_actor_grad(const ActorArgs& a, int H, int lds_bytes, hipStream_t s) {
   return mdp_for_width(H, [&](auto h) {
+    if (__builtin_expect(topo_any_squash(a.topo), 0)) {
+      ActorArgsSq q;
+      static_cast<ActorArgs&>(q) = a;
+      return launch_gen<k_actor_grad<h.value, ActorArgsSq>>(row_tiles(a.B), lds_bytes, s, q);
+    }
     return launch_gen<k_actor_grad<h.value>>(row_tiles(a.B), lds_bytes, s, a);
   });
 }

@@ -75,6 +75,10 @@ struct CriticArgsPer : CriticArgs {
   const float* is_w;
   float* td_out;
 };
+// a handle with a squashed Box agent (mdp_set_act_squash): the same
+// block under another type, which selects the instantiation whose samplers know
+// tanh; every other handle keeps the kernel it had
+struct CriticArgsSq : CriticArgs {};
 
 // MATD3 (strict mode, general kernels): the argument block of the critic
 // kernel's twin instantiation.  theta2 / target2 are param-space bases of the
@@ -170,6 +174,7 @@ struct ActorArgsHead {
 struct ActorArgs : ActorArgsHead {
   Topo topo;
 };
+struct ActorArgsSq : ActorArgs {};  // as CriticArgsSq
 struct ActorArgsMm : ActorArgs {  // M3DDPG, as CriticArgsMm
   float eps[MDP_MAX_AGENTS];
   float* adv_out;
@@ -452,7 +457,7 @@ struct EvalArgs {
   const float* u;
   uint64_t seed;
   uint32_t stream, ctr;
-  int act_w;  // gumbel: the agent's action space, kind bit | action width (topo_act_space)
+  int act_w;  // gumbel: the agent's action space, kind bit | squash bit | action width (topo_act_space)
 };
 
 // kernel width that serves --num-units u: the gradient / rollout / eval kernels

@@ -813,7 +813,9 @@ __device__ __forceinline__ void rollout_finish(const RolloutArgs& a, int64_t nex
 
 // MULTI: the a.nsteps > 1 instantiation (the one-step launch keeps its
 // straight-line schedule: a run-time loop around the body cost it 1.3 us)
-template <int H, bool MULTI>
+// (SQ: the instantiation for a handle with a squashed Box agent, DESIGN 26;
+// without one the samplers compile to what they were before the squash existed)
+template <int H, bool MULTI, bool SQ = false>
 __global__ __launch_bounds__(MDP_NT) void k_rollout(RolloutArgs a) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   MDP_TL_ROLLOUT();
@@ -980,7 +982,7 @@ __global__ __launch_bounds__(MDP_NT) void k_rollout(RolloutArgs a) {
           }
         }
         wave_sync();
-        if (lane < MDP_R) policy_sample(lgj + lane * 8, u, rowt + lane * ldr + aj.act_off, topo_act_space(T, j));
+        if (lane < MDP_R) policy_sample<SQ>(lgj + lane * 8, u, rowt + lane * ldr + aj.act_off, topo_act_space(T, j));
       }
       __syncthreads();
       MDP_STAMP(42);
@@ -1013,7 +1015,7 @@ __global__ __launch_bounds__(MDP_NT) void k_rollout(RolloutArgs a) {
         } else {
           uniforms5(a.seed, 0x10000u | (uint32_t)j, step_s(), (uint32_t)(a.env_base + e0 + tid), u);
         }
-        policy_sample(lg + tid * 8, u, dst, topo_act_space(T, j));
+        policy_sample<SQ>(lg + tid * 8, u, dst, topo_act_space(T, j));
       }
     }
     __syncthreads();
@@ -1141,7 +1143,7 @@ __global__ __launch_bounds__(MDP_NT) void k_rollout(RolloutArgs a) {
 // local_q agent's [obs_j | act_j] is staged into a tile behind k_rollout's carve
 // (lds_eval_q_bytes).  q and the step rewards of the valid rows go to global
 // memory; ret / bench are not written.  k_eval_returns folds them afterwards.
-template <int H, class Args = EvalEpArgs>
+template <int H, class Args = EvalEpArgs, bool SQ = false>
 __global__ __launch_bounds__(MDP_NT) void k_eval_episodes(Args a) {
   constexpr bool MU = std::is_same<Args, EvalMuArgs>::value;
   constexpr bool QV = std::is_same<Args, EvalQArgs>::value;
@@ -1233,7 +1235,7 @@ __global__ __launch_bounds__(MDP_NT) void k_eval_episodes(Args a) {
           uniforms5(a.seed, 0x70000u | (uint32_t)j, (uint32_t)t, a.first + (uint32_t)(i0 + row), u);
         }
       }
-      policy_sample_pre(logits, u, mean, dst, topo_act_space(T, j));
+      policy_sample_pre<SQ>(logits, u, mean, dst, topo_act_space(T, j));
     };
     // observations, one thread per (episode, agent); the listener hears the
     // speaker's action of the previous step (state.c; zero in the first)
@@ -1419,7 +1421,7 @@ __global__ __launch_bounds__(256) void k_eval_reset(EnvDesc env, uint64_t seed, 
 }
 
 // batched policy / critic evaluation for the facade (action, target_act, q_values)
-template <int H>
+template <int H, bool SQ = false>
 __global__ __launch_bounds__(MDP_NT) void k_mlp_eval(EvalArgs a) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const int ldx = lds_ld(a.in), ldh = H + 1;
@@ -1443,7 +1445,7 @@ __global__ __launch_bounds__(MDP_NT) void k_mlp_eval(EvalArgs a) {
       } else {
         uniforms5(a.seed, a.stream, a.ctr, (uint32_t)row, u);
       }
-      policy_sample(lg + tid * 8, u, act, (uint32_t)a.act_w);
+      policy_sample<SQ>(lg + tid * 8, u, act, (uint32_t)a.act_w);
       for (int k = 0; k < MDP_ACT_DIM; ++k) a.out[(int64_t)row * MDP_ACT_DIM + k] = act[k];
     } else {
       for (int k = 0; k < a.net.out; ++k) a.out[(int64_t)row * a.net.out + k] = lg[tid * 8 + k];
@@ -1471,6 +1473,17 @@ __global__ __launch_bounds__(MDP_NT) void k_mlp_eval(EvalArgs a) {
 MDP_ENV_KERNELS(64)
 MDP_ENV_KERNELS(128)
 MDP_ENV_KERNELS(256)
+// (behind all of them, so that those above lie where they lay)
+#define MDP_ENV_KERNELS_SQ(H)                                                \
+  template __global__ void k_rollout<H, false, true>(RolloutArgs);           \
+  template __global__ void k_rollout<H, true, true>(RolloutArgs);            \
+  template __global__ void k_mlp_eval<H, true>(EvalArgs);                    \
+  template __global__ void k_eval_episodes<H, EvalEpArgs, true>(EvalEpArgs); \
+  template __global__ void k_eval_episodes<H, EvalMuArgs, true>(EvalMuArgs); \
+  template __global__ void k_eval_episodes<H, EvalQArgs, true>(EvalQArgs);
+MDP_ENV_KERNELS_SQ(64)
+MDP_ENV_KERNELS_SQ(128)
+MDP_ENV_KERNELS_SQ(256)
 static int row_tiles(int rows) { return (rows + MDP_R - 1) / MDP_R; }
 template <auto K, typename A>
 static hipError_t launch_env(const dim3& grid, int lds, hipStream_t s, const A& a) {
@@ -1480,12 +1493,21 @@ static hipError_t launch_env(const dim3& grid, int lds, hipStream_t s, const A& 
 hipError_t mdp_launch_rollout(const RolloutArgs& a, int H, int lds_bytes, hipStream_t s) {
   const dim3 grid(row_tiles(a.E) + (a.pf_count > 0 ? 1 : 0));
   return mdp_for_width(H, [&](auto h) {
+    if (__builtin_expect(topo_any_squash(a.topo), 0)) {
+      if (a.nsteps > 1) return launch_env<k_rollout<h.value, true, true>>(grid, lds_bytes, s, a);
+      return launch_env<k_rollout<h.value, false, true>>(grid, lds_bytes, s, a);
+    }
     if (a.nsteps > 1) return launch_env<k_rollout<h.value, true>>(grid, lds_bytes, s, a);
     return launch_env<k_rollout<h.value, false>>(grid, lds_bytes, s, a);
   });
 }
 hipError_t mdp_launch_eval(const EvalArgs& a, int H, int lds_bytes, hipStream_t s) {
   return mdp_for_width(H, [&](auto h) {  // (never timed: a plain launch)
+    if (a.gumbel && ((uint32_t)a.act_w & 12u) == 12u) {  // a squashed Box agent's sample
+      mdp_raise_lds_limit<k_mlp_eval<h.value, true>, MDP_ENV_LDS_LIMIT>();
+      hipLaunchKernelGGL((k_mlp_eval<h.value, true>), dim3(row_tiles(a.rows)), dim3(MDP_NT), lds_bytes, s, a);
+      return hipGetLastError();
+    }
     mdp_raise_lds_limit<k_mlp_eval<h.value>, MDP_ENV_LDS_LIMIT>();
     hipLaunchKernelGGL(k_mlp_eval<h.value>, dim3(row_tiles(a.rows)), dim3(MDP_NT), lds_bytes, s, a);
     return hipGetLastError();
@@ -1493,6 +1515,8 @@ hipError_t mdp_launch_eval(const EvalArgs& a, int H, int lds_bytes, hipStream_t 
 }
 hipError_t mdp_launch_eval_episodes(const EvalEpArgs& a, int H, int lds_bytes, hipStream_t s) {
   return mdp_for_width(H, [&](auto h) {
+    if (__builtin_expect(topo_any_squash(a.topo), 0))
+      return launch_env<k_eval_episodes<h.value, EvalEpArgs, true>>(dim3(row_tiles(a.episodes)), lds_bytes, s, a);
     return launch_env<k_eval_episodes<h.value>>(dim3(row_tiles(a.episodes)), lds_bytes, s, a);
   });
 }
@@ -1500,11 +1524,16 @@ hipError_t mdp_launch_eval_episodes(const EvalEpArgs& a, int H, int lds_bytes, h
 // adjacent and share its weights in L2
 hipError_t mdp_launch_eval_matchups(const EvalMuArgs& a, int H, int lds_bytes, hipStream_t s) {
   return mdp_for_width(H, [&](auto h) {
+    if (__builtin_expect(topo_any_squash(a.topo), 0))
+      return launch_env<k_eval_episodes<h.value, EvalMuArgs, true>>(dim3(row_tiles(a.episodes), a.matchups), lds_bytes, s,
+                                                                 a);
     return launch_env<k_eval_episodes<h.value, EvalMuArgs>>(dim3(row_tiles(a.episodes), a.matchups), lds_bytes, s, a);
   });
 }
 hipError_t mdp_launch_eval_q(const EvalQArgs& a, int H, int lds_bytes, hipStream_t s) {
   return mdp_for_width(H, [&](auto h) {
+    if (__builtin_expect(topo_any_squash(a.topo), 0))
+      return launch_env<k_eval_episodes<h.value, EvalQArgs, true>>(dim3(row_tiles(a.episodes)), lds_bytes, s, a);
     return launch_env<k_eval_episodes<h.value, EvalQArgs>>(dim3(row_tiles(a.episodes)), lds_bytes, s, a);
   });
 }

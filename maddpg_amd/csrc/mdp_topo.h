@@ -46,14 +46,28 @@ struct Topo {
   // A Box actor's head is [mean (d) | logstd (d)], 2 d <= MDP_ACT_DIM wide in
   // the same W3 / b3 block; its action fills the first d entries of the slot
   // (topo_act_w is the ACTION width of either kind, topo_head_w the head's).
+  // A Box width needs two bits, so bit 2 of a Box agent's nibble is its squash
+  // (mdp_set_act_squash): 0 none, 1 tanh -- the action is tanh of the sample.
+  // The bit means nothing without the Box bit (a Discrete width may be 4 or 5),
+  // and changes no width: topo_act_w masks a Box agent's nibble with 3.
   uint32_t act_w4;
   float reg_scale_w[MDP_ACT_DIM];  // actor regulariser 2 * actor_reg / (B * A) for A = 1..5 (A < 5: ActorArgs::reg_scale is A = 5's)
 };
 #if defined(__HIPCC__)
 __host__ __device__
 #endif
-inline int topo_act_w(const Topo& t, int j) { return (int)((t.act_w4 >> (4 * j)) & 7u); }
-// agent j's whole nibble: kind bit | action width (the samplers' argument)
+inline int topo_act_w(const Topo& t, int j) {
+  const uint32_t s = t.act_w4 >> (4 * j);
+  return (int)(s & ((s & 8u) ? 3u : 7u));
+}
+// the same where no agent can be squashed (bit 2 is a width bit alone): the
+// kernels of a handle without a squash, and of the variants that refuse Box,
+// keep the mask they were compiled with before the squash existed
+#if defined(__HIPCC__)
+__host__ __device__
+#endif
+inline int topo_act_w7(const Topo& t, int j) { return (int)((t.act_w4 >> (4 * j)) & 7u); }
+// agent j's whole nibble: kind bit | squash bit | action width (the samplers' argument)
 #if defined(__HIPCC__)
 __host__ __device__
 #endif
@@ -67,6 +81,25 @@ inline bool topo_act_box(const Topo& t, int j) { return ((t.act_w4 >> (4 * j)) &
 __host__ __device__
 #endif
 inline int topo_head_w(const Topo& t, int j) { return topo_act_w(t, j) << (topo_act_box(t, j) ? 1 : 0); }
+#if defined(__HIPCC__)
+__host__ __device__
+#endif
+inline int topo_head_w7(const Topo& t, int j) { return topo_act_w7(t, j) << (topo_act_box(t, j) ? 1 : 0); }
+// a Box agent whose action is tanh of its sample (MDP_SQUASH_TANH)
+#if defined(__HIPCC__)
+__host__ __device__
+#endif
+inline bool topo_act_squash(const Topo& t, int j) { return ((t.act_w4 >> (4 * j)) & 12u) == 12u; }
+inline void topo_set_act_squash(Topo& t, int j, bool on) {  // (a Box agent only)
+  t.act_w4 = (t.act_w4 & ~(4u << (4 * j))) | ((on ? 4u : 0u) << (4 * j));
+}
+// some agent is squashed: the launchers then pick the kernels that know the squash
+inline bool topo_any_squash(const Topo& t) {
+  for (int j = 0; j < t.n; ++j)
+    if (topo_act_squash(t, j)) return true;
+  return false;
+}
+// (clears the squash: a Box width is at most 2)
 inline void topo_set_act_space(Topo& t, int j, bool box, int w) {
   t.act_w4 = (t.act_w4 & ~(15u << (4 * j))) | (((uint32_t)w | (box ? 8u : 0u)) << (4 * j));
 }

@@ -62,7 +62,7 @@ class Engine:
                  gamma=0.95, tau=1e-2, grad_clip=0.5, actor_reg=1e-3, adam_b1=0.9, adam_b2=0.999,
                  adam_eps=1e-8, seed=0, world_size=1, rank=0, device=None, episode_log_rows=0,
                  prioritized=False, per_alpha=0.6, per_beta0=0.4, per_beta_inc=0.001, per_eps=0.01,
-                 per_abs_err_upper=1.0, act_dims=None, act_kinds=None, td3=False, policy_delay=2, minimax=False, adv_eps=1e-3,
+                 per_abs_err_upper=1.0, act_dims=None, act_kinds=None, act_squash=None, td3=False, policy_delay=2, minimax=False, adv_eps=1e-3,
                  adv_eps_s=1e-5, minimax_eps=None, approx=False, approx_lambda=1e-3):
         """approx: MADDPG with inferred policies (mdp_approx_enable; Lowe et al. 2017,
         section 4.2) -- every agent i with a MADDPG critic learns an approximator of
@@ -86,7 +86,10 @@ class Engine:
         space, act_dims[i] in {1, 2}, and a diagonal-Gaussian policy whose head
         (actor_logits) is [mean | logstd], 2 act_dims[i] wide.  With a scenario,
         act_dims may be None: a box agent is Box(2), the others keep their own
-        space.  Strict mode, one GPU, none of prioritized / td3 / minimax / approx."""
+        space.  Strict mode, one GPU, none of prioritized / td3 / minimax / approx.
+        act_squash: per-agent None / "none" / "tanh" (or MDP_SQUASH_NONE 0 /
+        MDP_SQUASH_TANH 1; mdp_set_act_squash): a "tanh" agent, which must be a box
+        agent, plays tanh of its Gaussian sample, an action inside [-1, 1]."""
         # one variant per handle, on one GPU (variants.py): refused here, before
         # anything is allocated or created on the device
         minimax = bool(minimax) or minimax_eps is not None
@@ -187,6 +190,14 @@ class Engine:
             kk = (ctypes.c_int32 * _lib.MAX_AGENTS)()
             self._c("mdp_get_act_spaces", kk, None)
             self.act_kinds = ["box" if kk[i] == _lib.ACT_BOX else "discrete" for i in range(n)]
+        if act_squash is not None:
+            try:
+                if len(act_squash) != n:
+                    raise ValueError(f"act_squash needs one entry for each of the {n} agents")
+                self.set_act_squash(act_squash)
+            except (ValueError, _lib.MdpError) as e:
+                self.close()
+                raise ValueError(str(e)) from None
         lay = (ctypes.c_int32 * 6)()
         self.row_layout = []
         for i in range(n):
@@ -301,6 +312,28 @@ class Engine:
         kinds = (ctypes.c_int32 * _lib.MAX_AGENTS)(*[self._act_kind(k) for k in act_kinds])
         dims = (ctypes.c_int32 * _lib.MAX_AGENTS)(*[int(a) for a in act_dims])
         self._c("mdp_set_act_spaces", kinds, dims)
+
+    @staticmethod
+    def _squash(s):
+        if s in (None, "none", _lib.SQUASH_NONE):
+            return _lib.SQUASH_NONE
+        if s in ("tanh", _lib.SQUASH_TANH):
+            return _lib.SQUASH_TANH
+        raise ValueError(f"unknown action squash {s!r} (none, tanh)")
+
+    def set_act_squash(self, act_squash):
+        """mdp_set_act_squash on this handle (refused once it has been used)"""
+        sq = (ctypes.c_int32 * _lib.MAX_AGENTS)(*[self._squash(s) for s in act_squash])
+        self._c("mdp_set_act_squash", sq)
+
+    @property
+    def act_squash(self):
+        """per agent "none" / "tanh" (mdp_get_act_squash)"""
+        if not hasattr(self.lib, "mdp_get_act_squash"):   # an older build chosen with MDP_LIB (A/B)
+            return ["none"] * self.n
+        sq = (ctypes.c_int32 * _lib.MAX_AGENTS)()
+        self._c("mdp_get_act_squash", sq)
+        return ["tanh" if sq[i] == _lib.SQUASH_TANH else "none" for i in range(self.n)]
 
     def is_box(self, agent):
         return self.act_kinds[agent] == "box"
@@ -469,10 +502,22 @@ class Engine:
         return out
 
     def load_state_dict(self, sd, agents=None):
-        """agents: restore only these agents' parameter sets (None: every agent)"""
-        for i in range(self.n) if agents is None else sorted({int(a) for a in agents}):
+        """agents: restore only these agents' parameter sets (None: every agent).
+        sd["act_squash"] (an npz checkpoint's, Engine.load_state; a TF1 bundle has
+        no place for it) must be the handle's for every agent restored: the actors
+        were trained behind that squash."""
+        todo = list(range(self.n)) if agents is None else sorted({int(a) for a in agents})
+        for i in todo:
             if not 0 <= i < self.n:
                 raise ValueError(f"agent {i} out of range for {self.n} agents")
+        if "act_squash" in sd:
+            want = [int(v) for v in np.asarray(sd["act_squash"]).ravel()]
+            have = [self._squash(s) for s in self.act_squash]
+            if len(want) != self.n or any(want[i] != have[i] for i in todo):
+                names = {_lib.SQUASH_NONE: "none", _lib.SQUASH_TANH: "tanh"}
+                raise ValueError(f"the checkpoint's action squash {[names.get(v, v) for v in want]} differs from the "
+                                 f"handle's {[names[v] for v in have]} (Engine(act_squash=...), --action-squash)")
+        for i in todo:
             for w in self.SETS:
                 self.set_params(i, w, {k: sd[f"agent_{i}/{w}/{k}"] for k in TENSOR_NAMES})
             self.set_beta_powers(i, 0, sd[f"agent_{i}/actor/beta_power"])
@@ -526,7 +571,11 @@ class Engine:
         if d:
             os.makedirs(d, exist_ok=True)
         self._drop_stale(fname, keep="npz")
-        np.savez(path, **self.state_dict())
+        sd = self.state_dict()
+        sq = self.act_squash
+        if "tanh" in sq:    # (a TF1 bundle has no place for it: the squash is given again on restore)
+            sd["act_squash"] = np.array([self._squash(s) for s in sq], np.int32)
+        np.savez(path, **sd)
         return path
 
     def _drop_stale(self, fname, keep):
@@ -544,6 +593,8 @@ class Engine:
         two checkpoints); None restores every agent.  The checkpoint is read as
         read_checkpoint reads it."""
         sd, used = read_checkpoint(fname, self.checkpoint_path(fname), self.n, self.SETS)
+        if str(used).endswith(".npz") and "act_squash" not in sd:
+            sd["act_squash"] = np.zeros(self.n, np.int32)   # an npz without the array: no squash
         more = () if agents is None else (agents,)
         self.load_state_dict(sd, *more)
         return used

@@ -48,8 +48,14 @@ class VecRunner:
                  grad_clip=0.5, actor_reg=1e-3, prioritized=False, per_alpha=0.6, per_beta0=0.4,
                  per_beta_inc=0.001, per_eps=0.01, per_abs_err_upper=1.0, td3=False, policy_delay=2,
                  minimax=False, adv_eps=1e-3, adv_eps_s=1e-5, approx=False, approx_lambda=1e-3,
-                 continuous=False):
-        why = variants.runner_refusal(dict(prioritized=prioritized, td3=td3, minimax=minimax, approx=approx,
+                 continuous=False, squash=None):
+        """squash: None / "none" / "tanh" -- with continuous, every Box agent of the
+        scenario plays tanh of its Gaussian sample (Engine act_squash)"""
+        if squash not in (None, "none", "tanh"):
+            raise ValueError(f"unknown action squash {squash!r} (none, tanh)")
+        if squash == "tanh" and not continuous:
+            raise ValueError("--action-squash needs --continuous-actions")
+        why =variants.runner_refusal(dict(prioritized=prioritized, td3=td3, minimax=minimax, approx=approx,
                                            continuous=continuous), world_size)
         if why:
             raise ValueError(why)
@@ -68,7 +74,9 @@ class VecRunner:
                           per_abs_err_upper=per_abs_err_upper, td3=td3, policy_delay=policy_delay,
                           minimax=minimax, adv_eps=adv_eps, adv_eps_s=adv_eps_s, approx=approx,
                           approx_lambda=approx_lambda,
-                          **({"act_kinds": sp.act_kinds, "act_dims": sp.act_dims} if continuous else {}))
+                          **({"act_kinds": sp.act_kinds, "act_dims": sp.act_dims} if continuous else {}),
+                          **({"act_squash": ["tanh" if k == "box" else None for k in sp.act_kinds]}
+                             if squash == "tanh" else {}))
         self.eng.init_params(seed)                           # identical replicas on every rank
         self.eng.seed_py_random(seed + rank)                 # per-rank index stream
         self.eng.env_reset()

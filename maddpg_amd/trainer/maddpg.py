@@ -95,6 +95,12 @@ class MADDPGAgentTrainer(AgentTrainer):
                                           "d in (1, 2), are supported")
             self.act_dims.append(int(k))
             self.act_kinds.append("discrete")
+        # args.action_squash "tanh": every Box agent plays tanh of its sample (bounded
+        # actions); without the setting a Box entry stays a plain Gaussian
+        squash = getattr(args, "action_squash", "none") or "none"
+        if squash not in ("none", "tanh"):
+            raise ValueError(f"action_squash {squash!r}: none or tanh")
+        self.act_squash = [squash if k == "box" else "none" for k in self.act_kinds]
         self.session = U.get_session()
         self.session.register(self)
         self.replay_buffer = ReplayBuffer(1e6, _session=self.session, _agent=agent_index)

@@ -45,9 +45,23 @@ def box_muller(u, dtype=None):
     dt = dtype or trainer.F32
     u0, u1 = np.asarray(u[..., 0]).astype(dt), np.asarray(u[..., 1]).astype(dt)
     r = np.sqrt(dt(-2) * np.log(dt(1) - u0))
-    t = np.pi * (2.0 * u1.astype(np.float64))        # 2 u1 is exact; the reduction loses nothing
-    c, s = np.cos(t).astype(dt), np.sin(t).astype(dt)
-    return np.stack([r * c, r * s], -1).astype(dt)
+    c, s = sincospi2(u1)
+    return np.stack([r * c.astype(dt), r * s.astype(dt)], -1).astype(dt)
+
+
+def sincospi2(u1):
+    """(cos, sin) of 2 pi u1 in float64, reduced as sincospi(2 u1) reduces it: x = 2 u1
+    (exact) is split into the nearest multiple k / 2 of a quarter turn and a rest in
+    [-1/4, 1/4] (exact too), sin and cos are taken of pi * rest and rotated by k.
+    u1 in {0, 1/4, 1/2, 3/4} gives exact 0 and +-1, where cos(pi * 0.5) is 6.1e-17."""
+    x = 2.0 * np.asarray(u1).astype(np.float64)
+    k = np.rint(2.0 * x)
+    t = np.pi * (x - 0.5 * k)
+    c0, s0 = np.cos(t), np.sin(t)
+    q = k.astype(np.int64) & 3
+    c = np.choose(q, [c0, -s0, -c0, s0])
+    s = np.choose(q, [s0, c0, -s0, -c0])
+    return c + 0.0, s + 0.0                          # (-0 + 0 = +0: a quarter turn's zero carries no sign)
 
 
 def gaussian_sample(flat, u, d, dtype=None):

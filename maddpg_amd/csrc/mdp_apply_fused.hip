@@ -238,6 +238,14 @@ __device__ __forceinline__ float rows_sum(float v) {
 #endif
 }
 
+// Where chunk c's pair sits in its tensor's [MDP_RA_MAXCH][2] area, in 64-bit
+// words.  A tensor of at most MDP_RA_MAXCH / 4 chunks keeps its pairs 64 B
+// apart: packed 16 B apart, eight chunk workgroups' write-through stores and
+// every polling wave's loads met on one 128-B line, and a word stored to a
+// line that is being polled is seen late (tools/handoff_tagged_probe.hip,
+// DESIGN.md section 9)
+__device__ __forceinline__ int ra_pair_at(int c, int nch) { return 4 * nch <= MDP_RA_MAXCH ? 8 * c : 2 * c; }
+
 // The tensor's sum of squares from the chunks' pairs, exactly as the LDS body
 // reads them: lane q takes chunk q's pair once both tags carry this step's
 // epoch (bounded spin -> *faulted and Ctl::fault = 1)
@@ -245,7 +253,8 @@ __device__ __forceinline__ double chunks_poll(const uint64_t* part, int nch, uin
                                               bool* faulted) {
   double tot = 0.0;
   for (int q = lane; q < nch; q += 64) {
-    uint64_t hi = ld_agent64(part + 2 * q), lo = ld_agent64(part + 2 * q + 1);
+    const uint64_t* pq = part + ra_pair_at(q, nch);
+    uint64_t hi = ld_agent64(pq), lo = ld_agent64(pq + 1);
     uint32_t it = 0;
     while ((uint32_t)(hi >> 32) != nep || (uint32_t)(lo >> 32) != nep) {
       __builtin_amdgcn_s_sleep(1);
@@ -254,8 +263,8 @@ __device__ __forceinline__ double chunks_poll(const uint64_t* part, int nch, uin
         *faulted = true;
         break;
       }
-      hi = ld_agent64(part + 2 * q);
-      lo = ld_agent64(part + 2 * q + 1);
+      hi = ld_agent64(pq);
+      lo = ld_agent64(pq + 1);
     }
     tot += __longlong_as_double((long long)((hi << 32) | (lo & 0xffffffffull)));
   }
@@ -351,8 +360,8 @@ __device__ __forceinline__ void reduce_apply_lanes(const FusedApplyArgs& f, cons
   if (nch > 1 && threadIdx.x == 0) {
     const uint64_t tag = (uint64_t)nep << 32;
     const uint64_t bits = (uint64_t)__double_as_longlong(ss);
-    st_agent64(part + 2 * c, tag | (bits >> 32));
-    st_agent64(part + 2 * c + 1, tag | (bits & 0xffffffffull));
+    st_agent64(part + ra_pair_at(c, nch), tag | (bits >> 32));
+    st_agent64(part + ra_pair_at(c, nch) + 1, tag | (bits & 0xffffffffull));
   }
   const float gq = g == 0 ? s[0] : g == 1 ? s[1] : g == 2 ? s[2] : s[3];
   if (aact) a.grad[iq] = gq;
@@ -529,8 +538,8 @@ __device__ __forceinline__ void reduce_apply_body(const FusedApplyArgs& f, const
         // this chunk's fp64 sum of squares as two epoch-tagged 64-bit words
         // (high and low half) -- data and flag in one store, no counter RMW
         const uint64_t bits = (uint64_t)__double_as_longlong(ss);
-        st_agent64(part + 2 * c, tag | (bits >> 32));
-        st_agent64(part + 2 * c + 1, tag | (bits & 0xffffffffull));
+        st_agent64(part + ra_pair_at(c, nch), tag | (bits >> 32));
+        st_agent64(part + ra_pair_at(c, nch) + 1, tag | (bits & 0xffffffffull));
       }
       if (act && f.phase != 2) {
         if (p0 + 3 < n) {
@@ -551,7 +560,8 @@ __device__ __forceinline__ void reduce_apply_body(const FusedApplyArgs& f, const
         MDP_STAMP(32);
         tot = 0.0;
         for (int q = lane; q < nch; q += 64) {
-          uint64_t hi = ld_agent64(part + 2 * q), lo = ld_agent64(part + 2 * q + 1);
+          const uint64_t* pq = part + ra_pair_at(q, nch);
+          uint64_t hi = ld_agent64(pq), lo = ld_agent64(pq + 1);
           uint32_t it = 0;
           while ((uint32_t)(hi >> 32) != nep || (uint32_t)(lo >> 32) != nep) {
             __builtin_amdgcn_s_sleep(1);
@@ -560,8 +570,8 @@ __device__ __forceinline__ void reduce_apply_body(const FusedApplyArgs& f, const
               faulted = true;
               break;
             }
-            hi = ld_agent64(part + 2 * q);
-            lo = ld_agent64(part + 2 * q + 1);
+            hi = ld_agent64(pq);
+            lo = ld_agent64(pq + 1);
           }
           tot += __longlong_as_double((long long)((hi << 32) | (lo & 0xffffffffull)));
         }

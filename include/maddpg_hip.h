@@ -530,7 +530,15 @@ int mdp_evaluate_matchups(mdp_handle* h, const float* bank_dev, int32_t n_sets,
                           const int32_t* table_host, int32_t matchups,
                           int64_t first_episode, int32_t episodes, int32_t mode,
                           const float* u_dev, float* ret_dev, float* bench_dev);
-/* finished-episode log: total entries written so far, copy last `n` [n][1+n_agents] */
+/* finished-episode log, a ring of episode_log_rows entries [total | per agent]:
+ * mdp_episode_count is the number of entries written so far (`count`);
+ * mdp_episode_log copies entries [first, first + n) in the order they were
+ * logged into out_host[n][1 + n_agents].  Only the last episode_log_rows
+ * entries are live: the range must lie inside
+ * [max(0, count - episode_log_rows), count), and 0 <= n <= episode_log_rows.
+ * A range that reaches an overwritten or a not yet written entry is refused
+ * (< 0, the message names mdp_episode_log and the live window); nothing is
+ * copied then.  Both calls synchronise the handle's stream. */
 int64_t mdp_episode_count(mdp_handle* h);
 int mdp_episode_log(mdp_handle* h, int64_t first, int64_t n, float* out_host);
 

@@ -3669,7 +3669,20 @@ int64_t mdp_episode_count(mdp_handle* h) {
 int mdp_episode_log(mdp_handle* h, int64_t first, int64_t n, float* out) {
   MDP_NEED(h);
   const int64_t cap = h->L.eplog_rows, w = 1 + h->cfg.n_agents;
-  if (n > cap || first < 0) return fail(h, "episode log request exceeds ring");
+  if (n < 0 || n > cap || first < 0)
+    return fail(h, "mdp_episode_log: need first >= 0 and 0 <= n <= episode_log_rows");
+  if (n > 0 && !out) return fail(h, "mdp_episode_log: out_host is null");
+  // only the last `cap` entries are in the ring: an older one has been
+  // overwritten, a later one is not written yet (stale or zero rows either way)
+  int64_t count = 0;
+  HIPCHK(h, hipMemcpyAsync(&count, &h->ctl->episodes, 8, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  if (first + n > count || first < count - cap) {
+    const std::string m = "mdp_episode_log: entries [" + std::to_string(first) + ", " + std::to_string(first + n) +
+                          ") are outside the live window [" + std::to_string(std::max<int64_t>(0, count - cap)) +
+                          ", " + std::to_string(count) + ")";
+    return fail(h, m.c_str());
+  }
   int64_t done = 0;
   while (done < n) {  // at most two contiguous spans of the ring
     const int64_t slot = (first + done) % cap;

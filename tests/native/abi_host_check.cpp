@@ -605,6 +605,10 @@ static void lifecycle(const mdp_config& c, const char* name) {
     CHECK_OK(h, mdp_episode_log(h, eps_done - 4, 4, log.data()));
     CHECK_ERR(h, mdp_episode_log(h, 0, int64_t(1) << 40, log.data()));
     CHECK_ERR(h, mdp_episode_log(h, -1, 1, log.data()));
+    CHECK_ERR(h, mdp_episode_log(h, eps_done, 1, log.data()));      // not written yet
+    CHECK_ERR(h, mdp_episode_log(h, eps_done - 4, -1, log.data()));
+    CHECK_ERR(h, mdp_episode_log(h, eps_done - 4, 4, nullptr));
+    CHECK_OK(h, mdp_episode_log(h, eps_done, 0, nullptr));          // the empty range at the end of the window
     HIP_OR_DIE(hipFree(eobs));
   }
   // replay buffer entry points

@@ -39,9 +39,12 @@ def eps_matrix(name, kind):
     return minimax_eps(n, 0, 0.3, 0.3)
 
 
-def make_case(name, kind, seed=SEED):
-    """the case's replay, weights and noise with ReLU-margin-clean rows for eps `kind`"""
-    kw = CASES[name]
+def make_case(name, kind, seed=SEED, spec=None, prepare=None):
+    """the case's replay, weights and noise with ReLU-margin-clean rows for eps `kind`.
+    spec: a shape outside CASES (same keys); kind may be an n x n matrix; prepare(c)
+    puts a constructed state into the weights / replay before the rows are cleaned
+    (tests/minimax_edges.py)"""
+    kw = CASES[name] if spec is None else spec
     dims, H, B = kw["dims"], kw["H"], kw["B"]
     widths = kw.get("widths")
     if widths is None:
@@ -49,13 +52,17 @@ def make_case(name, kind, seed=SEED):
         c["widths"] = [5] * len(dims)
     else:
         c = mixed_width.mixed_case(dims, widths, B, L, seed, kw.get("local_q"), H)
-    c["eps"] = eps_matrix(name, kind)
+    c["spec"] = kw
+    c["eps"] = eps_matrix(name, kind) if isinstance(kind, str) else np.asarray(kind, np.float32)
+    if prepare is not None:
+        prepare(c)
     c["replaced"] = mo.clean_idx(c, c["widths"], c["eps"])
     return c
 
 
 def oracle_agents(c):
-    return [trainer.AgentParams(**copy.deepcopy(p), local_q=c["local_q"][j]) for j, p in enumerate(c["params"])]
+    return [trainer.AgentParams(**copy.deepcopy(p), local_q=c["local_q"][j], lr=c.get("lr", 1e-2))
+            for j, p in enumerate(c["params"])]
 
 
 def batches(c, i, idx=None):

@@ -318,7 +318,13 @@ def clean_idx(c, widths, eps, margin=1e-5, max_iter=40):
     def pre(p, x):
         p = _p(p, F64)
         z1 = x @ p["W1"] + p["b1"]
-        return [z1, np.maximum(z1, 0) @ p["W2"] + p["b2"]]
+        z2 = np.maximum(z1, 0) @ p["W2"] + p["b2"]
+        # a row with every layer-1 unit inactive has h1 == 0 and z2 == b2 exactly in any
+        # arithmetic: its layer 2 has no rounding to keep a margin from (section 28, case A)
+        dead = (z1 < 0).all(1)
+        if dead.any():
+            z2[dead] = 1.0 if dead.all() else np.abs(z2[~dead]).max()
+        return [z1, z2]
 
     def bad(zs):
         out = np.zeros(zs[0].shape[0], bool)

@@ -29,10 +29,11 @@ UPD_CTR = 642   # Ctl::upd_ctr, in 32-bit words (mdp_topo.h)
 def _engine(c, name, eps="case", **kw):
     """a handle of case `name` with c's replay and weights; eps: the case's matrix
     ("case"), None (a MADDPG handle) or a matrix"""
-    k = mc.CASES[name]
+    k = c["spec"] if "spec" in c else mc.CASES[name]
     mixed = any(w != 5 for w in c["widths"])
     if isinstance(eps, str):
         eps = c["eps"]
+    kw.setdefault("lr", c.get("lr", 1e-2))
     eng = Engine(k["dims"], c["local_q"], num_units=k["H"], batch_size=k["B"], capacity=mc.L + 7,
                  act_dims=c["widths"] if mixed else None, minimax_eps=eps, **kw)
     rows = mixed_width.joint_rows_w(c["data"], k["dims"]) if mixed else joint_rows(c["data"], k["dims"])
@@ -147,6 +148,33 @@ def _adv_check(got, want_n, ss, own, widths, eps_row, tag):
     return got[:, own]
 
 
+def _update_parity(eng, ags, c, i, tag):
+    """agent i's update on the handle and on the oracle agents (both move), held to the
+    tolerances of the module docstring; returns (device stats, oracle stats, oracle extras)"""
+    _update(eng, c, i)
+    got = eng.stats(i)
+    want, ex = mc.oracle_update(ags, c, i)
+    print(f"{tag} agent {i}: stats {got} oracle {want}")
+    assert abs(got[0] - want[0]) <= 1e-5 * abs(want[0]) + 1e-7, (i, got[0], want[0])
+    np.testing.assert_allclose(got[1:], want[1:], rtol=2e-5, atol=2e-6)
+    for w, ref in (("g_critic", ex["grad_critic"]), ("g_actor", ex["grad_actor"])):
+        dg = eng.get_params(i, w)
+        for k in ref:
+            r = np.asarray(ref[k], np.float64).reshape(dg[k].shape)
+            scale = float(np.abs(r).max()) or 1.0
+            err = float(np.abs(dg[k] - r).max()) / scale
+            assert err < 1e-5, (i, w, k, err)
+    sets = {"actor": ags[i].actor, "critic": ags[i].critic, "tgt_actor": ags[i].tgt_actor,
+            "tgt_critic": ags[i].tgt_critic, "m_actor": ags[i].opt_actor.m, "v_actor": ags[i].opt_actor.v,
+            "m_critic": ags[i].opt_critic.m, "v_critic": ags[i].opt_critic.v}
+    for w, ref in sets.items():
+        dev = eng.get_params(i, w)
+        for k in ref:
+            err = float(np.abs(dev[k] - np.asarray(ref[k]).reshape(dev[k].shape)).max())
+            assert err < 2e-4, (i, w, k, err)
+    return got, want, ex
+
+
 @pytest.mark.parametrize("kind", mc.EPS)
 @pytest.mark.parametrize("name", list(mc.CASES))
 def test_update_parity_and_perturbed_actions(name, kind):
@@ -159,27 +187,7 @@ def test_update_parity_and_perturbed_actions(name, kind):
     for i in range(n):
         adv_c.zero_()
         adv_a.zero_()
-        _update(eng, c, i)
-        got = eng.stats(i)
-        want, ex = mc.oracle_update(ags, c, i)
-        print(f"{name} {kind} agent {i}: stats {got} oracle {want}")
-        assert abs(got[0] - want[0]) <= 1e-5 * abs(want[0]) + 1e-7, (i, got[0], want[0])
-        np.testing.assert_allclose(got[1:], want[1:], rtol=2e-5, atol=2e-6)
-        for w, ref in (("g_critic", ex["grad_critic"]), ("g_actor", ex["grad_actor"])):
-            dg = eng.get_params(i, w)
-            for k in ref:
-                r = np.asarray(ref[k], np.float64).reshape(dg[k].shape)
-                scale = float(np.abs(r).max()) or 1.0
-                err = float(np.abs(dg[k] - r).max()) / scale
-                assert err < 1e-5, (i, w, k, err)
-        sets = {"actor": ags[i].actor, "critic": ags[i].critic, "tgt_actor": ags[i].tgt_actor,
-                "tgt_critic": ags[i].tgt_critic, "m_actor": ags[i].opt_actor.m, "v_actor": ags[i].opt_actor.v,
-                "m_critic": ags[i].opt_critic.m, "v_critic": ags[i].opt_critic.v}
-        for w, ref in sets.items():
-            dev = eng.get_params(i, w)
-            for k in ref:
-                err = float(np.abs(dev[k] - np.asarray(ref[k]).reshape(dev[k].shape)).max())
-                assert err < 2e-4, (i, w, k, err)
+        _, _, ex = _update_parity(eng, ags, c, i, f"{name} {kind}")
         gc, ga = adv_c.cpu().numpy(), adv_a.cpu().numpy()
         if c["local_q"][i]:           # today's kernels ran: nothing is written
             assert not gc.any() and not ga.any()

@@ -122,6 +122,11 @@ def parse_args(argv=None):
                         help="--continuous-actions: tanh puts every Box agent's sample through tanh, an action "
                              "inside [-1, 1] (the force a * accel is then bounded, as a Discrete(5) agent's is). "
                              "npz checkpoints record it; with a TF1 bundle give the flag again on restore")
+    parser.add_argument("--entropy-alpha", type=float, default=0.0,
+                        help="--continuous-actions: every Box agent's entropy coefficient (soft MADDPG: the agent "
+                             "maximises its reward plus alpha times its own policy's entropy; fixed). 0: none. Each "
+                             "learning-curve line is then followed by an entropy: line, the per-agent mean of -log pi. "
+                             "npz checkpoints record it; with a TF1 bundle give the flag again on restore")
     parser.add_argument("--approx-lambda", type=float, default=1e-3,
                         help="--approx-policies: weight of the approximators' entropy regulariser")
     # device-side policy evaluation (whole episodes in one launch; training state untouched)
@@ -443,6 +448,11 @@ def continuous_flags(arglist, world=1):
     """--continuous-actions is Box spaces; --action-squash is a setting of theirs"""
     if getattr(arglist, "action_squash", "none") != "none" and not getattr(arglist, "continuous_actions", False):
         raise SystemExit("--action-squash needs --continuous-actions")
+    alpha = getattr(arglist, "entropy_alpha", 0.0) or 0.0
+    if not (alpha >= 0 and alpha != float("inf")):
+        raise SystemExit("--entropy-alpha must be finite and >= 0")
+    if alpha and not getattr(arglist, "continuous_actions", False):
+        raise SystemExit("--entropy-alpha needs --continuous-actions")
     _combination("--continuous-actions", arglist, world)
 
 
@@ -482,6 +492,7 @@ def _make_runner(arglist, VecRunner, world, rank, per):
                        episode_log_rows=max(4096, 4 * arglist.num_envs, arglist.save_rate + 2 * arglist.num_envs),
                        continuous=getattr(arglist, "continuous_actions", False),
                        squash=getattr(arglist, "action_squash", "none"),
+                       entropy_alpha=getattr(arglist, "entropy_alpha", 0.0),
                        **per, **td3_kwargs(arglist), **minimax_kwargs(arglist), **approx_kwargs(arglist))
     if arglist.update_mode != "strict":
         runner.eng.set_update_mode(arglist.update_mode)
@@ -546,6 +557,12 @@ def _train(arglist, runner, exp_name, world, rank):
             else:
                 print("steps: {}, episodes: {}, mean episode reward: {}, agent episode reward: {}, time: {}".format(
                     steps, length, mean_ep, mean_ag, round(time.time() - t_start, 3)), flush=True)
+            if getattr(arglist, "entropy_alpha", 0.0):
+                # per agent the mean of -log pi over its last actor step's batch (0: no coefficient)
+                ent = [-runner.eng.entropy_info(i)["logp"] if a else 0.0
+                       for i, a in enumerate(runner.eng.act_entropy)]
+                print("entropy: episodes: {}, alpha: {}, mean -log pi: {}".format(
+                    length, arglist.entropy_alpha, ent), flush=True)
             if arglist.approx_policies:
                 # the approximators' fit on a fresh draw of replay rows (the training index stream stays put)
                 aq = runner.eng.approx_quality()

@@ -194,6 +194,46 @@ int mdp_get_act_spaces(const mdp_handle* h, int32_t kinds[MDP_MAX_AGENTS], int32
 int mdp_set_act_squash(mdp_handle* h, const int32_t squash[MDP_MAX_AGENTS]);
 /* the squashes in use (0 beyond n_agents and for a Discrete agent) */
 int mdp_get_act_squash(const mdp_handle* h, int32_t squash[MDP_MAX_AGENTS]);
+/* A Box agent's entropy coefficient: soft MADDPG.  Agent i, Box(d), plain or
+ * tanh-squashed, with alpha_i > 0 maximises its reward plus alpha_i times its own
+ * policy's entropy.  Sampling does not change.  For a sample with noise eps,
+ * pre-squash value z_k = mean_k + exp(logstd_k) * eps_k and action a_k (formed as
+ * above), its log-probability, in float, every product and sum rounded on its own
+ * (no fma), expf / log1pf libm's precise forms, in this order:
+ *   g_k = ((-0.5f * (eps_k * eps_k)) - logstd_k) - 0.5 ln(2 pi)
+ *   squashed:  w = |z_k|;  g_k = g_k - 2.0f * ((ln 2 - w) - log1pf(expf(-2.0f * w)))
+ *   lp = g_0                 (d = 1)
+ *   lp = g_0 + g_1           (d = 2)
+ * The squash term is ln(1 - tanh^2 z_k), finite at every finite z (also where the
+ * float action is exactly +-1).
+ * Critic step of agent i (MADDPG or DDPG critic): lp' = the log-probability of
+ * agent i's OWN target-actor sample at o'_i, the sample the step draws anyway;
+ * qs = q' - alpha_i * lp' in float (product, then difference), and the TD line runs
+ * with it: y = r + gamma (1 - done) (double)qs.  No other agent's entropy enters.
+ * mdp_get_stats' mean target q is the mean of qs.
+ * Actor step of agent i: the loss gains alpha_i * mean_b(lp_b) of the fresh own
+ * sample, and the gradient goes through the reparameterised sample at fixed eps.
+ * With ab = alpha_i / B (float division), per row and k < d, added (one rounded add)
+ * to the backward's dmean_k / dlogstd_k after the regulariser:
+ *   plain:     dlogstd_k += -ab                      (dmean_k gains nothing)
+ *   squashed:  dmean_k += ab * (2.0f * a_k)
+ *              dlogstd_k += ab * ((2.0f * a_k) * se_k - 1.0f),  se_k = std_k * eps_k
+ * p_loss (mdp_get_stats [1]) includes alpha_i * mean_b(lp_b).  With alpha_i = 0 agent
+ * i's update is what it is without the call, bit for bit; MDP_EVAL_MEAN, the
+ * evaluation calls, mdp_act and replay do not change.  The next action comes from
+ * the TARGET actor, the critic is single and alpha is fixed.
+ * alpha[i] >= 0 and finite for each of the n_agents agents; a negative or
+ * non-finite entry and a non-zero entry for a Discrete agent are refused with a
+ * message that names the call and the agent, a null pointer with one that names
+ * the call.  Accepted when mdp_set_act_squash is;
+ * mdp_set_act_spaces and mdp_set_act_dims reset every coefficient to 0. */
+int mdp_set_act_entropy(mdp_handle* h, const float* alpha /* [n_agents] */);
+/* the coefficients in use, alpha[n_agents] */
+int mdp_get_act_entropy(const mdp_handle* h, float* alpha);
+/* out = {alpha, mean lp of the agent's last actor step, mean lp' of its last critic
+ * step, 0} (0 before the first, and for an agent whose coefficient is 0); waits for
+ * the stream.  Refused on a handle on which no agent has a coefficient. */
+int mdp_entropy_info(mdp_handle* h, int32_t agent, double out[4]);
 
 /* ---- parameters (golden injection, checkpoint; tf_util.py:259-273) --- */
 int mdp_set_params(mdp_handle* h, int32_t agent, int32_t which, const float* src_host, int64_t n);

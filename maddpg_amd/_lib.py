@@ -110,6 +110,9 @@ SIGNATURES = {
     "mdp_get_act_spaces": (ctypes.c_int, [_P, _I32P, _I32P]),
     "mdp_set_act_squash": (ctypes.c_int, [_P, _I32P]),
     "mdp_get_act_squash": (ctypes.c_int, [_P, _I32P]),
+    "mdp_set_act_entropy": (ctypes.c_int, [_P, _F32P]),
+    "mdp_get_act_entropy": (ctypes.c_int, [_P, _F32P]),
+    "mdp_entropy_info": (ctypes.c_int, [_P, _I32, ctypes.POINTER(ctypes.c_double)]),
     "mdp_set_params": (ctypes.c_int, [_P, _I32, _I32, _F32P, _I64]),
     "mdp_get_params": (ctypes.c_int, [_P, _I32, _I32, _F32P, _I64]),
     "mdp_get_beta_powers": (ctypes.c_int, [_P, _I32, _I32, _F32P]),

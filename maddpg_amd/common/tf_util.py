@@ -65,7 +65,8 @@ class Session:
         obs_dims = [int(np.prod(s)) for s in t0.obs_shape_n]
         local_q = [bool(by_index[i].local_q_func) if i in by_index else False for i in range(n)]
         for t in self.trainers:
-            if t.act_dims != t0.act_dims or t.act_kinds != t0.act_kinds or t.act_squash != t0.act_squash:
+            if t.act_dims != t0.act_dims or t.act_kinds != t0.act_kinds or t.act_squash != t0.act_squash \
+                    or t.act_entropy != t0.act_entropy:
                 raise ValueError("trainers disagree on the action spaces")
         seed = self.seed if self.seed is not None else int(getattr(args, "seed", 0) or 0)
         self._engine = Engine(obs_dims, local_q, num_units=args.num_units, batch_size=args.batch_size,
@@ -73,6 +74,7 @@ class Session:
                               gamma=args.gamma, seed=seed, act_dims=t0.act_dims,
                               act_kinds=t0.act_kinds if "box" in t0.act_kinds else None,
                               act_squash=t0.act_squash if "tanh" in t0.act_squash else None,
+                              act_entropy=t0.act_entropy if any(t0.act_entropy) else None,
                               num_adversaries=int(getattr(args, "num_adversaries", 0) or 0), **per_kwargs(args),
                               **td3_kwargs(args), **minimax_kwargs(args), **approx_kwargs(args))
         self._engine.init_params(seed)

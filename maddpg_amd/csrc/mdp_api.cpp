@@ -334,6 +334,13 @@ struct mdp_handle {
   // grad kernels (mdp_grads.hip) -- lets tests compare both paths
   bool general_grads = false;
   bool box = false;  // some agent has a Box space (mdp_set_act_spaces; grads_r_ok then refuses the register kernels)
+  // entropy coefficients of the Box agents (mdp_set_act_entropy): an
+  // agent whose alpha is not 0 runs the gradient kernels' entropy instantiations.
+  // ent_out [n][2]: mean log pi of its last actor step, mean log pi' of its last
+  // critic step (k_entropy_fold), allocated with the first non-zero coefficient
+  float ent_alpha[MDP_MAX_AGENTS] = {};
+  bool ent_any = false;
+  double* ent_out = nullptr;
   // single-GPU optimizer step as one k_reduce_apply launch (MDP_UNFUSED_APPLY=1: k_reduce + k_apply)
   bool fused_apply = true;
   // ... with the reduced gradient kept in registers where mdp_ra_lanes allows
@@ -884,6 +891,17 @@ int do_critic_grad(mdp_handle* h, int agent, const int32_t* idx, const float* u_
     HIPCHK(h, mdp_launch_critic_grad_mm(m, h->L.topo.H, lds, h->stream));
     return 0;
   }
+  if (h->ent_alpha[agent] != 0.f && !tp) {  // the soft target (a Box handle: none of the variants above)
+    CriticArgsEnt e;
+    static_cast<CriticArgs&>(e) = a;
+    e.alpha = h->ent_alpha[agent];
+    while (e.group > 1 && lds_critic_ent_bytes(h->L.topo, e.group) > MDP_LDS_BUDGET) --e.group;
+    const int lds = lds_critic_ent_bytes(h->L.topo, e.group);
+    if (lds > MDP_LDS_BUDGET) return fail(h, "critic step does not fit in LDS");
+    HIPCHK(h, mdp_launch_critic_grad_ent(e, h->L.topo.H, lds, h->stream));
+    HIPCHK(h, mdp_launch_entropy_fold(e.slab_stat, h->L.nwg, e.B, h->ent_out + 2 * agent + 1, h->stream));
+    return 0;
+  }
   if (lds_critic_bytes(h->L.topo, a.group) > MDP_LDS_BUDGET) return fail(h, "critic step does not fit in LDS");
   if (apx_agent(h, agent) && !tp) {  // the others' target actions from this agent's target approximators
     CriticArgsApx x;
@@ -952,6 +970,15 @@ int do_actor_grad(mdp_handle* h, int agent, const int32_t* idx, const float* u_a
     for (int j = 0; j < MDP_MAX_AGENTS; ++j) m.eps[j] = h->mm_eps[agent][j];
     m.adv_out = h->mm_adv_a;
     HIPCHK(h, mdp_launch_actor_grad_mm(m, h->L.topo.H, lds_actor_mm_bytes(h->L.topo), h->stream));
+    return 0;
+  }
+  if (h->ent_alpha[agent] != 0.f && !tp) {  // + alpha * mean log pi of the fresh sample
+    ActorArgsEnt e;
+    static_cast<ActorArgs&>(e) = a;
+    e.alpha = h->ent_alpha[agent];
+    e.alpha_b = e.alpha / (float)a.B;
+    HIPCHK(h, mdp_launch_actor_grad_ent(e, h->L.topo.H, lds_actor_bytes(h->L.topo), h->stream));
+    HIPCHK(h, mdp_launch_entropy_fold(e.slab_stat, h->L.nwg, e.B, h->ent_out + 2 * agent, h->stream));
     return 0;
   }
   HIPCHK(h, mdp_launch_actor_grad(a, h->L.topo.H, lds_actor_bytes(h->L.topo), h->stream));
@@ -2185,6 +2212,7 @@ int mdp_destroy(mdp_handle* h) {
   if (!h) return 0;
   if (h->stream) (void)hipStreamSynchronize(h->stream);
   if (h->tp_list) (void)hipFree(h->tp_list);
+  if (h->ent_out) (void)hipFree(h->ent_out);
   for (int k = 0; k < MDP_K_COUNT; ++k)
     for (auto e : h->ev[k]) (void)hipEventDestroy(e);
   destroy_graphs(h, true);
@@ -2226,6 +2254,12 @@ int mdp_tensor(const mdp_handle* h, int32_t agent, int32_t net, int32_t t, mdp_t
   return 0;
 }
 
+// (mdp_set_act_dims / mdp_set_act_spaces: every entropy coefficient back to 0)
+static void ent_reset(mdp_handle* h) {
+  for (int i = 0; i < MDP_MAX_AGENTS; ++i) h->ent_alpha[i] = 0.f;
+  h->ent_any = false;
+}
+
 // per-agent action widths (Discrete(A_i), A_i in 1..MDP_ACT_DIM).  No layout
 // depends on them (every slot stays MDP_ACT_DIM wide, pad entries zero), but
 // the zeros must be in place before anything is written or launched, and
@@ -2249,6 +2283,7 @@ int mdp_set_act_dims(mdp_handle* h, const int32_t dims[MDP_MAX_AGENTS]) {
   }
   for (int i = 0; i < n; ++i) topo_set_act_w(h->L.topo, i, dims[i]);  // (every kind Discrete)
   h->box = false;
+  ent_reset(h);
   return 0;
 }
 
@@ -2290,6 +2325,7 @@ int mdp_set_act_spaces(mdp_handle* h, const int32_t kinds[MDP_MAX_AGENTS], const
   if (box && gate(h, Seam::BoxSpace)) return -1;
   for (int i = 0; i < n; ++i) topo_set_act_space(h->L.topo, i, kinds[i] == MDP_ACT_BOX, dims[i]);
   h->box = box;
+  ent_reset(h);
   return 0;
 }
 
@@ -2328,6 +2364,62 @@ int mdp_get_act_squash(const mdp_handle* h, int32_t squash[MDP_MAX_AGENTS]) {
   if (unusable(h) || !squash) return -1;
   for (int i = 0; i < MDP_MAX_AGENTS; ++i)
     squash[i] = i < h->cfg.n_agents && topo_act_squash(h->L.topo, i) ? MDP_SQUASH_TANH : MDP_SQUASH_NONE;
+  return 0;
+}
+
+// a Box agent's entropy coefficient.  It lives on the handle and in
+// the argument blocks of the agent's gradient launches; the Topo, the arena and
+// every sampler outside the two gradient kernels know nothing of it.  Accepted
+// where mdp_set_act_squash is: captured graphs hold the coefficients.
+int mdp_set_act_entropy(mdp_handle* h, const float* alpha) {
+  MDP_NEED(h);
+  if (!alpha) return fail(h, "mdp_set_act_entropy: alpha is null");
+  if (h->started || h->trained)
+    return fail(h, "mdp_set_act_entropy: call it before the handle's first parameter write, act, update or env call");
+  const int n = h->cfg.n_agents;
+  bool any = false;
+  char b[160];
+  for (int i = 0; i < n; ++i) {
+    if (!std::isfinite(alpha[i]) || alpha[i] < 0.f) {
+      std::snprintf(b, sizeof(b), "mdp_set_act_entropy: agent %d's coefficient must be finite and >= 0", i);
+      return fail(h, b);
+    }
+    if (alpha[i] != 0.f && !topo_act_box(h->L.topo, i)) {
+      std::snprintf(b, sizeof(b), "mdp_set_act_entropy: agent %d is Discrete: only a Box agent (mdp_set_act_spaces) "
+                                  "may carry an entropy coefficient", i);
+      return fail(h, b);
+    }
+    any = any || alpha[i] != 0.f;
+  }
+  if (any && lds_critic_ent_bytes(h->L.topo, 1) > MDP_LDS_BUDGET)
+    return fail(h, "mdp_set_act_entropy: the soft critic step does not fit in LDS");
+  if (any && !h->ent_out) {
+    HIPCHK(h, hipMalloc((void**)&h->ent_out, sizeof(double) * 2 * MDP_MAX_AGENTS));
+    HIPCHK(h, hipMemset(h->ent_out, 0, sizeof(double) * 2 * MDP_MAX_AGENTS));
+  }
+  for (int i = 0; i < MDP_MAX_AGENTS; ++i) h->ent_alpha[i] = i < n ? alpha[i] + 0.f : 0.f;  // (-0 -> +0)
+  h->ent_any = any;
+  return 0;
+}
+
+int mdp_get_act_entropy(const mdp_handle* h, float* alpha) {
+  if (unusable(h) || !alpha) return -1;
+  for (int i = 0; i < h->cfg.n_agents; ++i) alpha[i] = h->ent_alpha[i];
+  return 0;
+}
+
+int mdp_entropy_info(mdp_handle* h, int32_t agent, double out[4]) {
+  MDP_NEED(h);
+  if (!out) return fail(h, "mdp_entropy_info: out is null");
+  if (agent < 0 || agent >= h->cfg.n_agents) return fail(h, "mdp_entropy_info: agent out of range");
+  if (!h->ent_any) return fail(h, "mdp_entropy_info: no agent of this handle has an entropy coefficient (mdp_set_act_entropy)");
+  double v[2];
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  HIPCHK(h, hipMemcpy(v, h->ent_out + 2 * agent, sizeof(v), hipMemcpyDeviceToHost));
+  out[0] = (double)h->ent_alpha[agent];
+  out[1] = v[0];
+  out[2] = v[1];
+  out[3] = 0.0;
   return 0;
 }
 

@@ -40,6 +40,9 @@ MDP_HD inline int lds_ld(int cols) { return (cols | 1); }
   X(int, cnt, MDP_MAX_AGENTS + 4) /* layer-1 units done per net, then the work-queue counter (fwd_phase_l12) */
 // TWIN tail: the rows' fp32 TD target, kept for critic 2's loss seed
 #define MDP_CARVE_TWIN(X) X(float, ys, MDP_R)
+// ENT tail (critic_body, A = CriticArgsEnt): log pi of the agent's own target
+// sample of the tile's rows, from the sampling lanes to wave 0's TD line
+#define MDP_CARVE_ENT(X) X(float, lpt, MDP_R)
 // MM tail (critic_body and actor_body): the rows' gradient to every action column
 #define MDP_CARVE_MM(X, n_agents) X(float, dxa, MDP_R * MDP_ACT_DIM * (n_agents))
 // actor_body

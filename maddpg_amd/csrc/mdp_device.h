@@ -619,6 +619,81 @@ __device__ __forceinline__ void policy_sample(const float* head, const float* u,
   policy_sample_pre<SQ>(head, u, false, a, sp, se);
 }
 
+// Entropy-regularised Box policies (mdp_set_act_entropy): the forms of
+// the kernels that know an entropy coefficient.  They know the squash bit too.
+// log pi of a sample, from its noise eps_k, its pre-squash value z_k and the head
+// (include/maddpg_hip.h writes the order once; every product and sum rounded on
+// its own, libm's precise expf / log1pf):
+//   g_k = ((-0.5 * (eps_k * eps_k)) - logstd_k) - 0.5 ln(2 pi)
+//   squashed: w = |z_k|, g_k = g_k - 2 * ((ln 2 - w) - log1pf(expf(-2 * w)))
+//   lp = g_0 (+ g_1)
+// The squash term is ln(1 - tanh^2 z), finite at every finite z (where a = +-1.0f,
+// |z| >= 9, ln(1 - a^2) would be -inf).
+#define MDP_HALF_LN_2PI 0.918938533204672742f
+#define MDP_LN_2 0.693147180559945309f
+__device__ __forceinline__ float gauss_logprob_k(float logstd, float eps, float z, bool squash) {
+  float g = __fsub_rn(__fsub_rn(__fmul_rn(-0.5f, __fmul_rn(eps, eps)), logstd), MDP_HALF_LN_2PI);
+  if (squash) {
+    const float w = fabsf(z);
+    const float c = __fsub_rn(__fsub_rn(MDP_LN_2, w), log1pf(expf(__fmul_rn(-2.0f, w))));
+    g = __fsub_rn(g, __fmul_rn(2.0f, c));
+  }
+  return g;
+}
+// gauss_sample_pre<true> that also returns lp: the same z, a and se, bit for bit
+__device__ __forceinline__ float gauss_sample_lp(const float* flat, const float* eps, float* a, int d, float* se,
+                                                 bool squash) {
+  float lp = 0.f;
+#pragma unroll
+  for (int k = 0; k < MDP_ACT_DIM; ++k) a[k] = 0.f;
+#pragma unroll
+  for (int k = 0; k < 2; ++k) {
+    if (k < d) {
+      const float s = __fmul_rn(expf(flat[d + k]), eps[k]);
+      const float z = __fadd_rn(flat[k], s);
+      a[k] = squash ? tanhf(z) : z;
+      if (se) se[k] = s;
+      const float g = gauss_logprob_k(flat[d + k], eps[k], z, squash);
+      lp = k == 0 ? g : __fadd_rn(lp, g);
+    }
+  }
+  return lp;
+}
+// policy_sample<true> that also returns the sample's log pi (0 for a Discrete agent,
+// which has no coefficient)
+__device__ __forceinline__ float policy_sample_lp(const float* head, const float* u, float* a, uint32_t sp,
+                                                  float* se = nullptr) {
+  if ((sp & 8u) != 0u) {
+    float eps[2];
+    gauss_noise2(u, eps);
+    return gauss_sample_lp(head, eps, a, (int)(sp & 3u), se, (sp & 4u) != 0u);
+  }
+  policy_sample_pre<true>(head, u, false, a, sp, se);
+  return 0.f;
+}
+// gauss_backward<true> + the gradient of alpha * mean_b(lp) through the
+// reparameterised sample at fixed eps; ab = alpha / B.  Per k < d, added to
+// gauss_backward's output: plain, dlogstd_k += -ab (dmean_k gains nothing: no
+// add); squashed (av: the sample), dmean_k += ab * (2 * a_k), dlogstd_k += ab *
+// ((2 * a_k) * se_k - 1)
+__device__ __forceinline__ void gauss_backward_ent(const float* flat, const float* da, const float* se, int d,
+                                                   float reg_scale, float* dflat, const float* av, float ab) {
+  gauss_backward<true>(flat, da, se, d, reg_scale, dflat, av);
+#pragma unroll
+  for (int k = 0; k < MDP_ACT_DIM; ++k) {
+    const int j = min(k < d ? k : k - d, 1);
+    if (k < 2 * d) {
+      if (av) {
+        const float a2 = __fmul_rn(2.0f, av[j]);
+        const float e = k < d ? a2 : __fsub_rn(__fmul_rn(a2, se[j]), 1.0f);
+        dflat[k] = __fadd_rn(dflat[k], __fmul_rn(ab, e));
+      } else if (k >= d) {
+        dflat[k] = __fadd_rn(dflat[k], -ab);
+      }
+    }
+  }
+}
+
 // ------------------------------------------------------ phase-parallel tiles
 // (k_critic_grad / k_actor_grad, 512-thread workgroups)  A "job" is one dense
 // layer Y[16][N] = act(X[16][K] @ W[K][N] + b) of one net; all jobs of a

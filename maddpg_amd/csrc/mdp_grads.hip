@@ -463,11 +463,15 @@ __device__ __forceinline__ void critic_backward(const float* th, const NDesc& nd
 // APX (A = CriticArgsApx): inferred policies -- the target action of every agent
 // j != agent comes from this agent's target approximator of j (a.apx_target,
 // agent j's actor span) instead of target actor j; MADDPG critics
+// ENT (A = CriticArgsEnt): the soft target -- log pi' of this agent's own target
+// sample goes from the sampling lanes through lpt to wave 0's TD line, which
+// runs with qs = q' - alpha * lp' (DESIGN 29); implies SQ
 template <int H, bool PER = false, class A = CriticArgs, bool TWIN = false, bool MM = false, bool APX = false,
-          bool SQ = false>
+          bool SQ = false, bool ENT = false>
 __device__ __forceinline__ void critic_body(const A& a, const Topo& T, const int blk) {
   static_assert(!(MM && (TWIN || PER)), "minimax combines with neither twin critics nor prioritized replay");
   static_assert(!(APX && (MM || TWIN || PER)), "inferred policies combine with none of the other options");
+  static_assert(!ENT || (SQ && !(MM || TWIN || PER || APX)), "an entropy coefficient belongs to a Box handle");
   // (no MDP_KARG_TOUCH here: at H = 128 it turned the kernel's 47 spilled
   // SGPRs into 91 spilled VGPRs)
   constexpr int NT = H / 16;
@@ -482,6 +486,8 @@ __device__ __forceinline__ void critic_body(const A& a, const Topo& T, const int
   if constexpr (TWIN) { MDP_CARVE_TWIN(MDP_CARVE_SET) }
   float* dxa = nullptr;  // MM: d q' / d (action columns) of the rows
   if constexpr (MM) { MDP_CARVE_MM(MDP_CARVE_SET, T.n) }
+  float* lpt = nullptr;  // ENT: log pi' of the rows' own target sample
+  if constexpr (ENT) { MDP_CARVE_ENT(MDP_CARVE_SET) }
 
   const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63, nw = blockDim.x >> 6;
   const int r0 = blk * MDP_R;
@@ -667,7 +673,12 @@ __device__ __forceinline__ void critic_body(const A& a, const Topo& T, const int
       } else {
         uniforms5(a.seed, (uint32_t)((a.agent << 8) | (j + 1)), ctr, (uint32_t)(r0 + row), u);
       }
-      policy_sample<SQ>(lg + jb * MDP_R * 8 + row * 8, u, act, topo_act_space(T, j));
+      if constexpr (ENT) {  // (the lanes cover several agents: only this agent's own lp' is kept)
+        const float lp = policy_sample_lp(lg + jb * MDP_R * 8 + row * 8, u, act, topo_act_space(T, j));
+        if (j == a.agent) lpt[row] = lp;
+      } else {
+        policy_sample<SQ>(lg + jb * MDP_R * 8 + row * 8, u, act, topo_act_space(T, j));
+      }
       const int dst = lq ? ag.obs_dim : T.sum_obs + MDP_ACT_DIM * j;
       for (int k = 0; k < MDP_ACT_DIM; ++k) xt[row * ldc + dst + k] = act[k];
     }
@@ -767,6 +778,9 @@ __device__ __forceinline__ void critic_body(const A& a, const Topo& T, const int
       const double done = (double)rowbuf[lane * ldr + ag.done_off];
       float qnf = lg[lane * 8];
       if constexpr (TWIN) qnf = fminf(qnf, lg[lane * 8 + 1]);  // clipped double-Q
+      if constexpr (ENT) {  // the soft value: reward plus alpha times the own policy's entropy
+        qnf = __fsub_rn(qnf, __fmul_rn(a.alpha, lpt[lane]));
+      }
       const double qn = (double)qnf;
       const double y64 = rew + a.gamma * (1.0 - done) * qn;
       const float y = (float)y64;
@@ -796,6 +810,10 @@ __device__ __forceinline__ void critic_body(const A& a, const Topo& T, const int
       st[1] = s_y;
       st[2] = s_r;
       st[3] = s_q;
+    }
+    if constexpr (ENT) {  // the tile's sum of lp', in the record's first free slot
+      const double s_lp = sum16(lane < nvalid ? (double)lpt[lane] : 0.0);
+      if (lane == 0) a.slab_stat[(int64_t)blk * 8 + 4] = s_lp;
     }
   }
   __syncthreads();
@@ -857,7 +875,9 @@ template <int H, bool PER = false, class A = CriticArgs, bool TWIN = false, bool
 __global__ __launch_bounds__(MDP_GEN_THREADS) void k_critic_grad(A a) {
   // (A = CriticArgsSq: a handle with a squashed Box agent, DESIGN 26 -- the target
   // actors' samples go through tanh where the agent's squash bit says so)
-  critic_body<H, PER, A, TWIN, MM, APX, std::is_same<A, CriticArgsSq>::value>(a, a.topo, blockIdx.x);
+  // (A = CriticArgsEnt: this agent has an entropy coefficient)
+  constexpr bool ENT = std::is_same<A, CriticArgsEnt>::value;
+  critic_body<H, PER, A, TWIN, MM, APX, ENT || std::is_same<A, CriticArgsSq>::value, ENT>(a, a.topo, blockIdx.x);
 }
 
 // AA: ActorArgs, or the Topo-less ActorArgsHead of a gradient-pair launch
@@ -865,8 +885,11 @@ __global__ __launch_bounds__(MDP_GEN_THREADS) void k_critic_grad(A a) {
 // backward to the other agents' replayed actions, those moved against Q (a
 // constant of the backward), the critic again on the moved input, and the
 // step's backward from there
-template <int H, class AA, bool MM = false, bool SQ = false>
+// ENT (AA = ActorArgsEnt): the loss gains alpha * mean_b(log pi) of the fresh
+// sample; lp rides in the free eighth entry of the row's av slot
+template <int H, class AA, bool MM = false, bool SQ = false, bool ENT = false>
 __device__ __forceinline__ void actor_body(const AA& a, const Topo& T, const int blk) {
+  static_assert(!ENT || (SQ && !MM), "an entropy coefficient belongs to a Box handle");
   constexpr int NT = H / 16;
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const ADesc& ag = T.ag[a.agent];
@@ -962,7 +985,11 @@ __device__ __forceinline__ void actor_body(const AA& a, const Topo& T, const int
         uniforms5(a.seed, (uint32_t)((a.agent << 8) | 0x80), ctr, (uint32_t)(r0 + lane), u);
       }
       // (a Box agent: std * eps, the backward's factor, behind the slot's 5 entries)
-      policy_sample<SQ>(lg + lane * 8, u, av + lane * 8, topo_act_space(T, a.agent), av + lane * 8 + MDP_ACT_DIM);
+      if constexpr (ENT)
+        av[lane * 8 + 7] =
+            policy_sample_lp(lg + lane * 8, u, av + lane * 8, topo_act_space(T, a.agent), av + lane * 8 + MDP_ACT_DIM);
+      else
+        policy_sample<SQ>(lg + lane * 8, u, av + lane * 8, topo_act_space(T, a.agent), av + lane * 8 + MDP_ACT_DIM);
       if (!par)
         for (int k = 0; k < MDP_ACT_DIM; ++k) x[lane * ldc + ag.a_in_off + k] = av[lane * 8 + k];
     }
@@ -1111,8 +1138,12 @@ __device__ __forceinline__ void actor_body(const AA& a, const Topo& T, const int
       if (__builtin_expect(topo_act_box(T, a.agent), 0)) {  // Gaussian head: dmean | dlogstd
         float g[MDP_ACT_DIM];
         // (a squashed agent: 1 - a^2 from the sample in the tile's first lanes)
-        gauss_backward<SQ>(lg + lane * 8, da + lane * 8, av + lane * 8 + MDP_ACT_DIM, aw >> 1, reg_scale, g,
-                           SQ && topo_act_squash(T, a.agent) ? av + lane * 8 : nullptr);
+        if constexpr (ENT)
+          gauss_backward_ent(lg + lane * 8, da + lane * 8, av + lane * 8 + MDP_ACT_DIM, aw >> 1, reg_scale, g,
+                             topo_act_squash(T, a.agent) ? av + lane * 8 : nullptr, a.alpha_b);
+        else
+          gauss_backward<SQ>(lg + lane * 8, da + lane * 8, av + lane * 8 + MDP_ACT_DIM, aw >> 1, reg_scale, g,
+                             SQ && topo_act_squash(T, a.agent) ? av + lane * 8 : nullptr);
         for (int k = 0; k < MDP_ACT_DIM; ++k) dl[lane * 8 + k] = lane < nvalid ? g[k] : 0.f;
       } else {
         float dot = 0.f;
@@ -1124,6 +1155,9 @@ __device__ __forceinline__ void actor_body(const AA& a, const Topo& T, const int
       }
       if (lane < nvalid) {
         s_q = (double)qv[lane * 8];
+        if constexpr (ENT) {  // p_loss = -mean(q - alpha lp) + the regulariser
+          s_q = s_q - (double)a.alpha * (double)av[lane * 8 + 7];
+        }
         for (int k = 0; k < MDP_ACT_DIM; ++k) {
           const double p = (double)lg[lane * 8 + k];
           s_p += p * p;
@@ -1136,6 +1170,10 @@ __device__ __forceinline__ void actor_body(const AA& a, const Topo& T, const int
       double* st = a.slab_stat + (int64_t)blk * 8;
       st[0] = s_q;
       st[1] = s_p;
+    }
+    if constexpr (ENT) {  // the tile's sum of lp, in the record's first free slot
+      const double s_lp = sum16(lane < nvalid ? (double)av[lane * 8 + 7] : 0.0);
+      if (lane == 0) a.slab_stat[(int64_t)blk * 8 + 4] = s_lp;
     }
   }
   __syncthreads();
@@ -1182,7 +1220,8 @@ __global__ __launch_bounds__(MDP_GEN_THREADS) void k_actor_grad(AA a) {
     MDP_KARG_TOUCH("s"(a.agent), "s"(a.slab_stride), "s"(a.cpre_agent), "s"(a.topo.n));
     MDP_KARG_TOUCH(MDP_KARG_ADESC(a.topo.ag[a.agent]));
   }
-  actor_body<H, AA, MM, std::is_same<AA, ActorArgsSq>::value>(a, a.topo, blockIdx.x);  // (as k_critic_grad)
+  constexpr bool ENT = std::is_same<AA, ActorArgsEnt>::value;
+  actor_body<H, AA, MM, ENT || std::is_same<AA, ActorArgsSq>::value, ENT>(a, a.topo, blockIdx.x);  // (as k_critic_grad)
 }
 
 // Inferred policies: one gradient step's raw gradients of the
@@ -1376,6 +1415,36 @@ hipError_t mdp_launch_actor_grad(const ActorArgs& a, int H, int lds_bytes, hipSt
     }
     return launch_gen<k_actor_grad<h.value>>(row_tiles(a.B), lds_bytes, s, a);
   });
+}
+
+// (behind every other kernel and launcher of this file, so that those above lie
+// in the code object where they lay before the entropy instantiations existed)
+// An agent's mean log pi (mdp_entropy_info): the launch before it left each
+// tile's sum in slot 4 of its slab_stat record, which the optimizer's stats
+// workgroup does not read.  One wave, lane-strided partial sums and the fixed
+// tree of that workgroup (deterministic, no float atomics).  (A template, so that it
+// is emitted where it is first used, here, and not ahead of the kernels above.)
+template <int LANES>
+__global__ __launch_bounds__(LANES) void k_entropy_fold(const double* slab_stat, int nwg, int B, double* out) {
+  static_assert(LANES == 64, "one wave: wave_sum_d");
+  double s = 0.0;
+  for (int w = threadIdx.x; w < nwg; w += LANES) s += slab_stat[(int64_t)w * 8 + 4];
+  s = wave_sum_d(s);
+  if (threadIdx.x == 0) out[0] = s / B;
+}
+hipError_t mdp_launch_critic_grad_ent(const CriticArgsEnt& a, int H, int lds_bytes, hipStream_t s) {
+  return mdp_for_width(H, [&](auto h) {
+    return launch_gen<k_critic_grad<h.value, false, CriticArgsEnt>>(row_tiles(a.B), lds_bytes, s, a);
+  });
+}
+hipError_t mdp_launch_actor_grad_ent(const ActorArgsEnt& a, int H, int lds_bytes, hipStream_t s) {
+  return mdp_for_width(H, [&](auto h) {
+    return launch_gen<k_actor_grad<h.value, ActorArgsEnt>>(row_tiles(a.B), lds_bytes, s, a);
+  });
+}
+hipError_t mdp_launch_entropy_fold(const double* slab_stat, int nwg, int B, double* out, hipStream_t s) {
+  hipLaunchKernelGGL(k_entropy_fold<64>, dim3(1), dim3(64), 0, s, slab_stat, nwg, B, out);
+  return hipGetLastError();
 }
 
 #ifdef MDP_STAMPS

@@ -79,6 +79,14 @@ struct CriticArgsPer : CriticArgs {
 // block under another type, which selects the instantiation whose samplers know
 // tanh; every other handle keeps the kernel it had
 struct CriticArgsSq : CriticArgs {};
+// agent's critic step with an entropy coefficient alpha != 0 (mdp_set_act_entropy,
+// DESIGN 29): the soft target, qs = q' - alpha * log pi'(a~_agent | o'_agent).  Its
+// samplers know the squash bit (one instantiation serves plain and squashed
+// agents); an agent whose coefficient is 0 keeps the kernel it had.  The tile's
+// sum of log pi' goes to slot 4 of its slab_stat record
+struct CriticArgsEnt : CriticArgs {
+  float alpha;
+};
 
 // MATD3 (strict mode, general kernels): the argument block of the critic
 // kernel's twin instantiation.  theta2 / target2 are param-space bases of the
@@ -175,6 +183,12 @@ struct ActorArgs : ActorArgsHead {
   Topo topo;
 };
 struct ActorArgsSq : ActorArgs {};  // as CriticArgsSq
+// agent's actor step with alpha != 0, as CriticArgsEnt: the loss gains alpha *
+// mean_b(log pi(a_b | o_b)) of the fresh sample; alpha_b = alpha / B in float.  Slot
+// 0 of the tile's record is the sum of q - alpha * log pi, slot 4 that of log pi
+struct ActorArgsEnt : ActorArgs {
+  float alpha, alpha_b;
+};
 struct ActorArgsMm : ActorArgs {  // M3DDPG, as CriticArgsMm
   float eps[MDP_MAX_AGENTS];
   float* adv_out;
@@ -482,6 +496,12 @@ inline int lds_actor_bytes(const Topo& t) {
   MDP_CARVE_ACTOR(MDP_CARVE_WORDS, lds_ld(t.row_stride), lds_ld(t.cin_max), MDP_R * (t.H + 1), t.H)
   return 4 * words;
 }
+// the entropy instantiation's tail (CriticArgsEnt)
+inline int lds_critic_ent_bytes(const Topo& t, int G) {
+  int words = 0;
+  MDP_CARVE_ENT(MDP_CARVE_WORDS)
+  return lds_critic_bytes(t, G) + 4 * words;
+}
 // the minimax instantiations' tail, in words
 inline int lds_mm_dxa(const Topo& t) {
   int words = 0;
@@ -626,6 +646,11 @@ inline hipError_t mdp_launch_lds(const dim3& grid, const dim3& block, int lds, h
 
 hipError_t mdp_launch_critic_grad(const CriticArgs& a, int H, int lds_bytes, hipStream_t s);
 hipError_t mdp_launch_actor_grad(const ActorArgs& a, int H, int lds_bytes, hipStream_t s);
+// an agent with an entropy coefficient (alpha != 0): its own instantiations
+hipError_t mdp_launch_critic_grad_ent(const CriticArgsEnt& a, int H, int lds_bytes, hipStream_t s);
+hipError_t mdp_launch_actor_grad_ent(const ActorArgsEnt& a, int H, int lds_bytes, hipStream_t s);
+// out[0] = (sum over the nwg records of slot 4) / B: the mean log pi of the launch before it
+hipError_t mdp_launch_entropy_fold(const double* slab_stat, int nwg, int B, double* out, hipStream_t s);
 hipError_t mdp_launch_grad_pair(const GradPairArgs& a, int H, int lds_bytes, hipStream_t s);
 hipError_t mdp_launch_critic_grad_r(const CriticArgs& a, int lds_bytes, hipStream_t s);
 hipError_t mdp_launch_critic_grad_per(const CriticArgsPer& a, int H, int lds_bytes, hipStream_t s);

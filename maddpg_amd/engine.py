@@ -62,7 +62,7 @@ class Engine:
                  gamma=0.95, tau=1e-2, grad_clip=0.5, actor_reg=1e-3, adam_b1=0.9, adam_b2=0.999,
                  adam_eps=1e-8, seed=0, world_size=1, rank=0, device=None, episode_log_rows=0,
                  prioritized=False, per_alpha=0.6, per_beta0=0.4, per_beta_inc=0.001, per_eps=0.01,
-                 per_abs_err_upper=1.0, act_dims=None, act_kinds=None, act_squash=None, td3=False, policy_delay=2, minimax=False, adv_eps=1e-3,
+                 per_abs_err_upper=1.0, act_dims=None, act_kinds=None, act_squash=None, act_entropy=None, td3=False, policy_delay=2, minimax=False, adv_eps=1e-3,
                  adv_eps_s=1e-5, minimax_eps=None, approx=False, approx_lambda=1e-3):
         """approx: MADDPG with inferred policies (mdp_approx_enable; Lowe et al. 2017,
         section 4.2) -- every agent i with a MADDPG critic learns an approximator of
@@ -89,7 +89,10 @@ class Engine:
         space.  Strict mode, one GPU, none of prioritized / td3 / minimax / approx.
         act_squash: per-agent None / "none" / "tanh" (or MDP_SQUASH_NONE 0 /
         MDP_SQUASH_TANH 1; mdp_set_act_squash): a "tanh" agent, which must be a box
-        agent, plays tanh of its Gaussian sample, an action inside [-1, 1]."""
+        agent, plays tanh of its Gaussian sample, an action inside [-1, 1].
+        act_entropy: per-agent entropy coefficient alpha_i >= 0 (None: 0;
+        mdp_set_act_entropy): a box agent with alpha_i > 0 maximises its reward plus
+        alpha_i times its own policy's entropy (soft MADDPG)."""
         # one variant per handle, on one GPU (variants.py): refused here, before
         # anything is allocated or created on the device
         minimax = bool(minimax) or minimax_eps is not None
@@ -196,6 +199,14 @@ class Engine:
                     raise ValueError(f"act_squash needs one entry for each of the {n} agents")
                 self.set_act_squash(act_squash)
             except (ValueError, _lib.MdpError) as e:
+                self.close()
+                raise ValueError(str(e)) from None
+        if act_entropy is not None:
+            try:
+                if len(act_entropy) != n:
+                    raise ValueError(f"act_entropy needs one entry for each of the {n} agents")
+                self.set_act_entropy(act_entropy)
+            except (ValueError, TypeError, _lib.MdpError) as e:
                 self.close()
                 raise ValueError(str(e)) from None
         lay = (ctypes.c_int32 * 6)()
@@ -334,6 +345,27 @@ class Engine:
         sq = (ctypes.c_int32 * _lib.MAX_AGENTS)()
         self._c("mdp_get_act_squash", sq)
         return ["tanh" if sq[i] == _lib.SQUASH_TANH else "none" for i in range(self.n)]
+
+    def set_act_entropy(self, act_entropy):
+        """mdp_set_act_entropy on this handle (refused once it has been used); None is 0"""
+        al = (ctypes.c_float * _lib.MAX_AGENTS)(*[0.0 if a is None else float(a) for a in act_entropy])
+        self._c("mdp_set_act_entropy", al)
+
+    @property
+    def act_entropy(self):
+        """per agent entropy coefficient (mdp_get_act_entropy)"""
+        if not hasattr(self.lib, "mdp_get_act_entropy"):   # an older build chosen with MDP_LIB (A/B)
+            return [0.0] * self.n
+        al = (ctypes.c_float * _lib.MAX_AGENTS)()
+        self._c("mdp_get_act_entropy", al)
+        return [float(al[i]) for i in range(self.n)]
+
+    def entropy_info(self, agent):
+        """mdp_entropy_info: {"alpha", "logp": mean log pi of the agent's last actor
+        step, "logp_target": mean log pi' of its last critic step}"""
+        out = (ctypes.c_double * 4)()
+        self._c("mdp_entropy_info", int(agent), out)
+        return {"alpha": out[0], "logp": out[1], "logp_target": out[2]}
 
     def is_box(self, agent):
         return self.act_kinds[agent] == "box"
@@ -517,6 +549,12 @@ class Engine:
                 names = {_lib.SQUASH_NONE: "none", _lib.SQUASH_TANH: "tanh"}
                 raise ValueError(f"the checkpoint's action squash {[names.get(v, v) for v in want]} differs from the "
                                  f"handle's {[names[v] for v in have]} (Engine(act_squash=...), --action-squash)")
+        if "act_entropy" in sd:
+            want = [float(np.float32(v)) for v in np.asarray(sd["act_entropy"]).ravel()]
+            have = self.act_entropy
+            if len(want) != self.n or any(want[i] != have[i] for i in todo):
+                raise ValueError(f"the checkpoint's entropy coefficients {want} differ from the handle's {have} "
+                                 f"(Engine(act_entropy=...), --entropy-alpha)")
         for i in todo:
             for w in self.SETS:
                 self.set_params(i, w, {k: sd[f"agent_{i}/{w}/{k}"] for k in TENSOR_NAMES})
@@ -575,6 +613,9 @@ class Engine:
         sq = self.act_squash
         if "tanh" in sq:    # (a TF1 bundle has no place for it: the squash is given again on restore)
             sd["act_squash"] = np.array([self._squash(s) for s in sq], np.int32)
+        al = self.act_entropy
+        if any(al):         # (as the squash: a TF1 bundle has no place for it)
+            sd["act_entropy"] = np.array(al, np.float32)
         np.savez(path, **sd)
         return path
 
@@ -595,6 +636,8 @@ class Engine:
         sd, used = read_checkpoint(fname, self.checkpoint_path(fname), self.n, self.SETS)
         if str(used).endswith(".npz") and "act_squash" not in sd:
             sd["act_squash"] = np.zeros(self.n, np.int32)   # an npz without the array: no squash
+        if str(used).endswith(".npz") and "act_entropy" not in sd:
+            sd["act_entropy"] = np.zeros(self.n, np.float32)   # ... and no entropy coefficient
         more = () if agents is None else (agents,)
         self.load_state_dict(sd, *more)
         return used

@@ -10,6 +10,7 @@ by E per vector step, so a round runs for every multiple of 100 crossed
 applies unchanged.  Index draws, gathers, both optimiser steps and Polyak
 updates run on the device in the reference's agent order.
 """
+import math
 import os
 from . import envs, variants
 from .engine import Engine
@@ -48,9 +49,16 @@ class VecRunner:
                  grad_clip=0.5, actor_reg=1e-3, prioritized=False, per_alpha=0.6, per_beta0=0.4,
                  per_beta_inc=0.001, per_eps=0.01, per_abs_err_upper=1.0, td3=False, policy_delay=2,
                  minimax=False, adv_eps=1e-3, adv_eps_s=1e-5, approx=False, approx_lambda=1e-3,
-                 continuous=False, squash=None):
+                 continuous=False, squash=None, entropy_alpha=0.0):
         """squash: None / "none" / "tanh" -- with continuous, every Box agent of the
-        scenario plays tanh of its Gaussian sample (Engine act_squash)"""
+        scenario plays tanh of its Gaussian sample (Engine act_squash)
+        entropy_alpha: with continuous, every Box agent's entropy coefficient
+        (Engine act_entropy; 0: none)"""
+        entropy_alpha = float(entropy_alpha or 0.0)
+        if not math.isfinite(entropy_alpha) or entropy_alpha < 0:
+            raise ValueError("--entropy-alpha must be finite and >= 0")
+        if entropy_alpha and not continuous:
+            raise ValueError("--entropy-alpha needs --continuous-actions")
         if squash not in (None, "none", "tanh"):
             raise ValueError(f"unknown action squash {squash!r} (none, tanh)")
         if squash == "tanh" and not continuous:
@@ -76,7 +84,9 @@ class VecRunner:
                           approx_lambda=approx_lambda,
                           **({"act_kinds": sp.act_kinds, "act_dims": sp.act_dims} if continuous else {}),
                           **({"act_squash": ["tanh" if k == "box" else None for k in sp.act_kinds]}
-                             if squash == "tanh" else {}))
+                             if squash == "tanh" else {}),
+                          **({"act_entropy": [entropy_alpha if k == "box" else 0.0 for k in sp.act_kinds]}
+                             if entropy_alpha else {}))
         self.eng.init_params(seed)                           # identical replicas on every rank
         self.eng.seed_py_random(seed + rank)                 # per-rank index stream
         self.eng.env_reset()

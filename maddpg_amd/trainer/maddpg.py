@@ -101,6 +101,11 @@ class MADDPGAgentTrainer(AgentTrainer):
         if squash not in ("none", "tanh"):
             raise ValueError(f"action_squash {squash!r}: none or tanh")
         self.act_squash = [squash if k == "box" else "none" for k in self.act_kinds]
+        # args.entropy_alpha: every Box agent's entropy coefficient (soft MADDPG); 0: none
+        alpha = float(getattr(args, "entropy_alpha", 0.0) or 0.0)
+        if not np.isfinite(alpha) or alpha < 0:
+            raise ValueError(f"entropy_alpha {alpha!r}: finite and >= 0")
+        self.act_entropy = [alpha if k == "box" else 0.0 for k in self.act_kinds]
         self.session = U.get_session()
         self.session.register(self)
         self.replay_buffer = ReplayBuffer(1e6, _session=self.session, _agent=agent_index)
